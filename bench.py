@@ -29,6 +29,9 @@ the oracle's chain after the timed region (the oracle is the checker here, never
 
 PyTorch is used for device memory, the stream and torch.distributed only; all pixel work goes
 through the C-ABI of libansel_hip.so (include/ansel_hip.h).  There is no CPU fallback.
+
+--dump-outputs DIR writes what the last timed step exported (the RGBA u16 words, as float32 .npy files; a fixed seeded
+sample of the pixels above 4 MP) so that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -72,7 +75,13 @@ def parse():
                          "between the devices ordered by events (no launcher; --gpus = devices, --bands = bands)")
     ap.add_argument("--bands", type=int, default=0, help="--mode bands: number of row bands (default: one per device); more "
                                                         "bands than devices puts several on a device (a one-GPU dry run)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the exported RGBA words of the last step to DIR/*.npy (float32; the whole "
+                         "frame up to 4 MP, a fixed seeded sample of its pixels above that), so that two builds can be compared")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def frame_size(name):
@@ -520,6 +529,39 @@ def full_pipe_leg(torch, np, pipe, synth, l, devid, dev, size, lut, lut_host, wi
     return leg
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: the most it writes, all files together
+DUMP_SAMPLE_DRAWS = 2_000_000  # pixels drawn (with replacement, then de-duplicated) when the frame exceeds the budget
+DUMP_SEED = 20240517
+
+
+def dump_outputs(dirpath, frame, width, height, prefix="", budget=DUMP_BYTES):
+    """--dump-outputs: the exported RGBA u16 words of the last timed step, as a caller of dt_hip_pipe_process receives them.
+    `frame` is (height, width, 4) 16-bit words: a device tensor (int16 view) or a host array.  Writes DIR/<prefix>export_rgba.npy
+    in float32 (every u16 is exact): the whole frame (height, width, 4) when it fits the budget, else the (n, 4) words of a
+    fixed seeded sample of pixels together with DIR/<prefix>export_rgba_pixel_index.npy (float64, row * width + column, sorted).
+    The sample depends on the frame size only, so two builds run with the same arguments write the same pixels."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    npix = width * height
+    words = frame.reshape(npix, 4)
+    idx = None
+    if npix * 4 * 4 > budget:
+        rng = np.random.default_rng(DUMP_SEED)
+        draws = min(DUMP_SAMPLE_DRAWS, budget // (4 * 4 + 8))
+        idx = np.unique(rng.integers(0, npix, draws))
+        if isinstance(words, np.ndarray):
+            words = words[idx]
+        else:
+            import torch
+            words = words[torch.from_numpy(idx).to(words.device)]
+    if not isinstance(words, np.ndarray):
+        words = words.cpu().numpy()
+    vals = np.ascontiguousarray(words).view(np.uint16).astype(np.float32)
+    np.save(os.path.join(dirpath, prefix + "export_rgba.npy"), vals if idx is not None else vals.reshape(height, width, 4))
+    if idx is not None:
+        np.save(os.path.join(dirpath, prefix + "export_rgba_pixel_index.npy"), idx.astype(np.float64))
+
+
 def band_digest(t):
     """64-bit digest of a band's exported words (host side, after the timed region)"""
     import xxhash
@@ -635,10 +677,13 @@ def bands_mode(args):
     elapsed = time.perf_counter() - t0
     st = abi.BandStats()
     l.dt_hip_pipe_bands_stats(C.byref(st))
+    whole = None
+    if args.dump_outputs or not args.no_verify:
+        whole = np.concatenate([t.cpu().numpy().view(np.uint16) for t in outs], axis=0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, whole, width, height)
     verify = None
     if not args.no_verify:
-        whole = np.concatenate([t.cpu().numpy().view(np.uint16) for t in outs], axis=0)
-
         class _H:  # verify_output() takes a tensor-like with .cpu().numpy()
             def cpu(self):
                 return self
@@ -764,6 +809,11 @@ def main():
 
     # ---- per-kernel HIP-event timings of the timed region (recorded on the launch stream)
     kernels = read_kernel_events(l, devid)
+
+    # ---- what the last timed step wrote (this rank's frame, or its band in --mode tiled), before anything else runs
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out16, width, my_rows, prefix="rank%d_" % rank if world > 1 else "",
+                     budget=DUMP_BYTES // world)
 
     # ---- --mode tiled validates itself (after the timed region): every rank digests the band its timed steps wrote, rank 0
     #      runs the SAME frame unsplit through the same executor and compares band by band -- the assembled bands are the

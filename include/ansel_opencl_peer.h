@@ -6,7 +6,7 @@
  * common/opencl.h: each dt_opencl_*() the host files call is an inline forward to its dt_hip_*() peer with the same
  * arguments and the same return convention (TRUE/FALSE where the reference returns gboolean, CL_SUCCESS = 0 or a
  * negative code where it returns cl_int, NULL from the allocators).  tests/test_boundary_compile.py compiles the
- * reference's pixelpipe_gpu.c and tiling.c, unmodified, against this header and runs them on the device.
+ * reference's pixelpipe_gpu.c and tiling.c, unmodified, against this header where the reference's sources are.
  *
  * What is NOT here, by design: the kernel table (dt_opencl_create_kernel / set_kernel_arg / enqueue_kernel_2d,
  * opencl.h:433-457).  Kernels are compiled into the library and reached through one entry point per module

@@ -7,7 +7,7 @@
  *   * modules written the way INTEGRATION.md section 2 tells a maintainer to write them (integration_stubs.h, over the
  *     reference's own dt_iop_<op>_data_t): `exposure` (pointwise) and `diffuse` (a stencil module: tiles overlap), and the
  *     blend stage dt_develop_blend_process_cl() behind a module that supports blending;
- *   * the drivers the test calls: the reference's pixelpipe_process_on_GPU() on exposure, plain and blended (device path,
+ *   * the drivers (boundary_run_*, called through ctypes): the reference's pixelpipe_process_on_GPU() on exposure, plain and blended (device path,
  *     output synced to the host cache line), and the reference's default_process_tiling_cl() on either module (host-tiled
  *     path, the budget squeezed so that the frame takes many tiles; every process_cl() call's region is logged).
  */
