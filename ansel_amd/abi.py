@@ -139,6 +139,16 @@ class FinalscaleData(C.Structure):
     _fields_ = [("interpolation", C.c_int)]
 
 
+# dt_image_orientation_t bits (the flip module's orientation)
+ORIENTATION_NONE, ORIENTATION_FLIP_Y, ORIENTATION_FLIP_X, ORIENTATION_SWAP_XY = 0, 1, 2, 4
+ORIENTATION_NULL = -1  # "use the image's orientation": resolved by params.flip()
+
+
+class FlipData(C.Structure):
+    """dt_hip_flip_data_t: the orientation, 0..7 (bits FLIP_Y = 1, FLIP_X = 2, SWAP_XY = 4)"""
+    _fields_ = [("orientation", C.c_int32)]
+
+
 class LabData(C.Structure):
     """dt_hip_lab_data_t: the 3x3 (rows padded to 4) of the RGB <-> Lab glue, and the tone curves of a work profile
     that has them"""

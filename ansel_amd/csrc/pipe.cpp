@@ -54,6 +54,7 @@ enum op_t
   OP_EXPORT_ROWS,
   OP_EXPORT_U8,
   OP_DETAILMASK,
+  OP_FLIP, // changes the geometry (SWAP_XY): never inside a fused group
   OP_UNKNOWN
 };
 
@@ -87,6 +88,7 @@ const op_info_t k_ops[] = {
   { "export_rows", sizeof(dt_hip_export_rows_t), 0 },
   { "export_u8", 0, 4 },
   { "detailmask", sizeof(dt_hip_detailmask_data_t), 16 },
+  { "flip", sizeof(dt_hip_flip_data_t), 0 },
 };
 
 struct node_t
@@ -113,7 +115,8 @@ size_t out_bytes(const node_t &n)
     case OP_RAWPREPARE: return px * 4;
     case OP_TEMPERATURE:
     case OP_HIGHLIGHTS:
-    case OP_EXPOSURE: return px * 4 * n.piece.channels;
+    case OP_EXPOSURE:
+    case OP_FLIP: return px * 4 * n.piece.channels;
     case OP_EXPORT_U16: return px * 8;
     case OP_EXPORT_U8: return px * 4;
     case OP_EXPORT_ROWS:
@@ -144,6 +147,7 @@ int run_single(int devid, const node_t &n, dt_hip_mem_t in, dt_hip_mem_t out)
     case OP_FINALSCALE: return dt_hip_iop_finalscale_process(devid, &n.piece, n.as<dt_hip_finalscale_data_t>(), in, out);
     case OP_INITIALSCALE: return dt_hip_iop_initialscale_process(devid, &n.piece, n.as<dt_hip_finalscale_data_t>(), in, out);
     case OP_DETAILMASK: return dt_hip_iop_detailmask_process(devid, &n.piece, n.as<dt_hip_detailmask_data_t>(), in, out);
+    case OP_FLIP: return dt_hip_iop_flip_process(devid, &n.piece, n.as<dt_hip_flip_data_t>(), in, out);
     case OP_EXPORT_U16: return dt_hip_export_convert_u16(devid, n.piece.roi_out.width, n.piece.roi_out.height, in, out);
     case OP_EXPORT_U8: return dt_hip_export_convert_u8(devid, n.piece.roi_out.width, n.piece.roi_out.height, in, out);
     case OP_EXPORT_ROWS:
@@ -160,6 +164,7 @@ struct dt_hip_pipe_t
   int devid;
   bool fusion;
   bool planned;
+  bool dropped_flip; // the last node added was a flip of orientation 0 (not kept)
   std::vector<node_t> nodes;
   std::vector<group_t> groups;
 
@@ -293,6 +298,7 @@ dt_hip_pipe_t *dt_hip_pipe_new(int devid)
   p->devid = devid;
   p->fusion = true;
   p->planned = false;
+  p->dropped_flip = false;
   return p;
 }
 
@@ -314,6 +320,36 @@ int dt_hip_pipe_add_node(dt_hip_pipe_t *pipe, const char *op, const dt_hip_piece
   {
     set_last_error("dt_hip_pipe_add_node: '%s' expects %zu bytes of data, got %zu", op, k_ops[o].data_size, data_size);
     return DT_HIP_INVALID_ARG;
+  }
+  if(o == OP_BLEND && (pipe->dropped_flip || (!pipe->nodes.empty() && pipe->nodes.back().op == OP_FLIP)))
+  {
+    set_last_error("dt_hip_pipe_add_node: flip has no blending (a 'blend' node cannot follow it)");
+    return DT_HIP_INVALID_ARG;
+  }
+  pipe->dropped_flip = false;
+  if(o == OP_FLIP)
+  {
+    const int orientation = ((const dt_hip_flip_data_t *)data)->orientation;
+    if(orientation < 0 || orientation > 7)
+    {
+      set_last_error("dt_hip_pipe_add_node: flip orientation %d is not one of 0..7 (resolve -1 to the image's orientation first)",
+                     orientation);
+      return DT_HIP_INVALID_ARG;
+    }
+    const bool swap = (orientation & 4) != 0;
+    if(piece->roi_out.width != (swap ? piece->roi_in.height : piece->roi_in.width)
+       || piece->roi_out.height != (swap ? piece->roi_in.width : piece->roi_in.height))
+    {
+      set_last_error("dt_hip_pipe_add_node: flip orientation %d: roi_out %d x %d is not roi_in %d x %d oriented", orientation,
+                     piece->roi_out.width, piece->roi_out.height, piece->roi_in.width, piece->roi_in.height);
+      return DT_HIP_INVALID_ARG;
+    }
+    if(orientation == 0)
+    {
+      // the identity: no node, so launches and words are those of the pipe without it
+      pipe->dropped_flip = true;
+      return DT_HIP_SUCCESS;
+    }
   }
   node_t n;
   n.op = o;
@@ -342,6 +378,14 @@ int dt_hip_pipe_process(dt_hip_pipe_t *pipe, dt_hip_mem_t dev_in, dt_hip_mem_t d
 {
   if(!pipe || !dev_in || !dev_out) return DT_HIP_INVALID_ARG;
   if(pipe->nodes.empty()) return DT_HIP_SUCCESS;
+  // flip passes its input format through: a consumer that reads another one would read past the flip's output
+  for(size_t k = 0; k + 1 < pipe->nodes.size(); k++)
+    if(pipe->nodes[k].op == OP_FLIP && pipe->nodes[k + 1].piece.channels != pipe->nodes[k].piece.channels)
+    {
+      set_last_error("pipe: the flip node has %u channels, the '%s' node behind it reads %u", pipe->nodes[k].piece.channels,
+                     k_ops[pipe->nodes[k + 1].op].name, pipe->nodes[k + 1].piece.channels);
+      return DT_HIP_INVALID_ARG;
+    }
   if(!pipe->planned) pipe->plan();
   const int devid = pipe->devid;
   dt_hip_mem_t cur = dev_in;
@@ -582,6 +626,7 @@ int band_halo_rows(const node_t &n)
     case OP_DENOISEPROFILE: return denoiseprofile_halo_rows(&n.piece, n.as<dt_hip_denoiseprofile_data_t>());
     case OP_DIFFUSE: return diffuse_halo_rows(&n.piece, n.as<dt_hip_diffuse_data_t>());
     case OP_NLMEANS: return nlmeans_halo_rows(&n.piece, n.as<dt_hip_nlmeans_data_t>());
+    case OP_FLIP: return n.as<dt_hip_flip_data_t>()->orientation == 0 ? 0 : -1;
     default: return 0;
   }
 }
@@ -961,6 +1006,13 @@ int dt_hip_pipe_band_begin(dt_hip_pipe_t *pipe, const dt_hip_band_t *band, dt_hi
   if(!pipe->planned) pipe->plan();
   const int devid = pipe->devid;
   const dt_hip_band_t &b = *band;
+  for(const node_t &n : pipe->nodes)
+    if(n.op == OP_FLIP)
+    {
+      // row bands of a transposed frame are columns of its input; a mirrored one would take another band's rows
+      set_last_error("band mode: 'flip' with orientation %d has no row-band implementation", (int)n.as<dt_hip_flip_data_t>()->orientation);
+      return DT_HIP_INVALID_ARG;
+    }
   const int W = pipe->nodes[0].piece.roi_out.width, H = pipe->nodes[0].piece.roi_out.height;
   for(const node_t &n : pipe->nodes)
     if(n.piece.roi_out.width != W || n.piece.roi_out.height != H)
@@ -1726,6 +1778,12 @@ int dt_hip_default_process_tiling_ptp(int devid, const char *op, const dt_hip_pi
     set_last_error("tiling: module '%s' cannot be tiled here", op);
     return DT_HIP_INVALID_ARG;
   }
+  if(n.op == OP_FLIP)
+  {
+    // a mirrored tile lands elsewhere in the output: flip is tiled by dt_hip_default_process_tiling_roi()
+    set_last_error("tiling: 'flip' moves pixels between tiles; use dt_hip_default_process_tiling_roi()");
+    return DT_HIP_INVALID_ARG;
+  }
   if(data_size) n.data.assign((const unsigned char *)data, (const unsigned char *)data + data_size);
   const dt_hip_roi_t &ri = piece->roi_in, &ro = piece->roi_out;
   if(ri.x != ro.x || ri.y != ro.y || ri.width != ro.width || ri.height != ro.height || ri.scale != ro.scale)
@@ -1799,8 +1857,8 @@ int dt_hip_default_process_tiling_ptp(int devid, const char *op, const dt_hip_pi
 }
 
 // ---- default_process_tiling_cl() for roi_in != roi_out, src/develop/tiling.c:1076-1390 (_default_process_tiling_cl_roi)
-// The only module of the export path whose output geometry differs from its input is finalscale, so its
-// modify_roi_in() (src/iop/finalscale.c:76-107, the full-resolution pipeline of an export) is the one restated here.
+// Two modules of the export path change the geometry: finalscale, whose modify_roi_in() (src/iop/finalscale.c:76-107,
+// the full-resolution pipeline of an export) is restated here, and flip (flip.hip, dt_hip_tile_rois_flip()).
 namespace
 {
 static int ra_align_up(const int n, const int a) { return n + a - (n % a); } // tiling.c:92-95: one more step even when aligned
@@ -1995,20 +2053,23 @@ int dt_hip_tile_rois_finalscale(const dt_hip_tile_plan_roi_t *pl, const dt_hip_r
 }
 
 // the loop of :1222-1370: host frame -> every tile's full input region through the device -> the good part of its
-// output back into the host frame.  `op` must be "finalscale" (the module whose modify_roi_in() is restated above)
+// output back into the host frame.  `op` is "finalscale" or "flip": the modules with a tile-region function
 int dt_hip_default_process_tiling_roi(int devid, const char *op, const dt_hip_piece_t *piece, const void *data, size_t data_size,
                                       const dt_hip_tiling_t *tiling, const void *host_in, void *host_out, int in_bpp,
                                       int out_bpp, size_t available_bytes)
 {
   if(!valid_device(devid) || !op || !piece || !tiling || !host_in || !host_out) return DT_HIP_INVALID_ARG;
-  if(strcmp(op, "finalscale") != 0)
+  node_t n;
+  if(!strcmp(op, "finalscale"))
+    n.op = OP_FINALSCALE;
+  else if(!strcmp(op, "flip"))
+    n.op = OP_FLIP;
+  else
   {
-    set_last_error("tiling (roi_in != roi_out): '%s' has no modify_roi_in() here; finalscale is the one module of the path that "
-                   "changes the geometry", op);
+    set_last_error("tiling (roi_in != roi_out): '%s' has no modify_roi_in() here; finalscale and flip are the modules of the "
+                   "path that change the geometry", op);
     return DT_HIP_INVALID_ARG;
   }
-  node_t n;
-  n.op = OP_FINALSCALE;
   if(data_size != k_ops[n.op].data_size || (data_size && !data)) return DT_HIP_INVALID_ARG;
   if(data_size) n.data.assign((const unsigned char *)data, (const unsigned char *)data + data_size);
   const dt_hip_roi_t &ri = piece->roi_in, &ro = piece->roi_out;
@@ -2025,7 +2086,9 @@ int dt_hip_default_process_tiling_roi(int devid, const char *op, const dt_hip_pi
     for(int ty = 0; ty < pl.tiles_y; ty++)
     {
       dt_hip_roi_t iroi_full, oroi_full, oroi_good;
-      err = dt_hip_tile_rois_finalscale(&pl, &ri, &ro, tx, ty, &iroi_full, &oroi_full, &oroi_good);
+      err = n.op == OP_FLIP
+              ? dt_hip_tile_rois_flip(&pl, &ri, &ro, n.as<dt_hip_flip_data_t>(), tx, ty, &iroi_full, &oroi_full, &oroi_good)
+              : dt_hip_tile_rois_finalscale(&pl, &ri, &ro, tx, ty, &iroi_full, &oroi_full, &oroi_good);
       if(err == DT_HIP_TILE_EMPTY) continue;
       if(err != DT_HIP_SUCCESS) return err;
       const size_t ioffs = (size_t)(iroi_full.y - ri.y) * ipitch + (size_t)(iroi_full.x - ri.x) * in_bpp;

@@ -907,6 +907,8 @@ size_t dt_hip_abi_sizeof(const char *name)
   S("finalscale", dt_hip_finalscale_data_t);
   S("blend", dt_hip_blend_data_t);
   S("detailmask", dt_hip_detailmask_data_t);
+  S("flip", dt_hip_flip_data_t);
+  S("tile_plan_roi", dt_hip_tile_plan_roi_t);
   S("export_rows", dt_hip_export_rows_t);
   S("tile_plan", dt_hip_tile_plan_t);
   S("band", dt_hip_band_t);

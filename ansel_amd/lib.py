@@ -125,6 +125,11 @@ def load():
         "dt_hip_iop_bilat_process": (i, [i, P(abi.Piece), P(abi.BilatData), vp, vp]),
         "dt_hip_iop_finalscale_process": (i, [i, P(abi.Piece), P(abi.FinalscaleData), vp, vp]),
         "dt_hip_iop_initialscale_process": (i, [i, P(abi.Piece), P(abi.FinalscaleData), vp, vp]),
+        "dt_hip_iop_flip_process": (i, [i, P(abi.Piece), P(abi.FlipData), vp, vp]),
+        "dt_hip_iop_flip_modify_roi_out": (i, [P(abi.FlipData), i, i, P(abi.Roi), P(abi.Roi)]),
+        "dt_hip_iop_flip_modify_roi_in": (i, [P(abi.FlipData), i, i, P(abi.Roi), P(abi.Roi)]),
+        "dt_hip_iop_flip_distort_transform": (i, [P(abi.FlipData), i, i, P(C.c_float), sz]),
+        "dt_hip_iop_flip_distort_backtransform": (i, [P(abi.FlipData), i, i, P(C.c_float), sz]),
         "dt_hip_raw_unpack": (i, [i, vp, i, i, C.c_size_t, i, i, vp]),
         "dt_hip_develop_blend_process": (i, [i, P(abi.Piece), P(abi.BlendData), vp, vp]),
         "dt_hip_iop_basebuffer_process": (i, [i, P(abi.Piece), i, i, i, vp, vp]),
@@ -136,6 +141,8 @@ def load():
         "dt_hip_default_tiling": (None, [P(abi.Piece), i, P(abi.Tiling)]),
         "dt_hip_plan_tiles_roi": (i, [P(abi.Roi), P(abi.Roi), i, i, P(abi.Tiling), C.c_uint, sz, sz, i, i, P(abi.TilePlanRoi)]),
         "dt_hip_tile_rois_finalscale": (i, [P(abi.TilePlanRoi), P(abi.Roi), P(abi.Roi), i, i, P(abi.Roi), P(abi.Roi), P(abi.Roi)]),
+        "dt_hip_tile_rois_flip": (i, [P(abi.TilePlanRoi), P(abi.Roi), P(abi.Roi), P(abi.FlipData), i, i, P(abi.Roi), P(abi.Roi),
+                                      P(abi.Roi)]),
         "dt_hip_default_process_tiling_roi": (i, [i, C.c_char_p, P(abi.Piece), vp, sz, P(abi.Tiling), vp, vp, i, i, sz]),
         "dt_hip_iop_denoiseprofile_tiling": (None, [P(abi.Piece), P(abi.DenoiseprofileData), P(abi.Tiling)]),
         "dt_hip_iop_nlmeans_tiling": (None, [P(abi.Piece), P(abi.NlmeansData), P(abi.Tiling)]),

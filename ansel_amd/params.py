@@ -192,3 +192,26 @@ def denoiseprofile(color_mode=abi.DT_HIP_DENOISEPROFILE_Y0U0V0, use_new_vst=True
     for k in range(4):
         d.wb_coeffs[k] = wbc[k] if k < len(wbc) else 0.0
     return d
+
+
+# ---- orientation (src/iop/flip.c) -------------------------------------------------------------
+# the EXIF Orientation tag (1..8) -> the dt_image_orientation_t that shows the frame upright (include/ansel_hip.h,
+# the table under dt_hip_flip_data_t)
+EXIF_ORIENTATION = {1: 0, 2: abi.ORIENTATION_FLIP_X, 3: abi.ORIENTATION_FLIP_Y | abi.ORIENTATION_FLIP_X,
+                    4: abi.ORIENTATION_FLIP_Y, 5: abi.ORIENTATION_SWAP_XY,
+                    6: abi.ORIENTATION_SWAP_XY | abi.ORIENTATION_FLIP_Y, 7: 7,
+                    8: abi.ORIENTATION_SWAP_XY | abi.ORIENTATION_FLIP_X}
+
+
+def flip(orientation=abi.ORIENTATION_NULL, image_orientation=0):
+    """dt_hip_flip_data_t as commit_params() fills it: the module's orientation, or with -1 (ORIENTATION_NULL, the module
+    default) the image's own orientation (from its EXIF tag: EXIF_ORIENTATION)"""
+    o = int(image_orientation) if int(orientation) == abi.ORIENTATION_NULL else int(orientation)
+    if not 0 <= o <= 7:
+        raise ValueError("orientation %d is not one of 0..7" % o)
+    return abi.FlipData(o)
+
+
+def oriented_size(width, height, orientation):
+    """the frame's size after the flip module"""
+    return (height, width) if orientation & abi.ORIENTATION_SWAP_XY else (width, height)

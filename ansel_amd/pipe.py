@@ -18,6 +18,7 @@ MODULE_BPP = {
     "exposure": (16, 16), "colorin": (16, 16), "channelmixerrgb": (16, 16), "filmicrgb": (16, 16),
     "colorout": (16, 16), "export_u16": (16, 8), "rgb_to_lab": (16, 16), "lab_to_rgb": (16, 16), "nlmeans": (16, 16),
     "bilat": (16 + 16, 16),  # splat reads L, slice reads + writes the plane (48 B/px)
+    "flip": (16, 16),
 }
 
 
@@ -28,10 +29,32 @@ class Node:
         self.piece = piece
 
 
+def insert_flip(nodes, after_op, orientation, image_orientation=0):
+    """the flip module right behind the node `after_op`: orientation 0..7, or -1 for image_orientation (params.flip()).
+    The nodes behind it get the oriented geometry (their pieces are copied, not changed in place)."""
+    data = params.flip(orientation, image_orientation)
+    k = [n.op for n in nodes].index(after_op)
+    # flip's input format is what the next module reads (a piece describes its module's INPUT: behind demosaic, whose own
+    # piece is the mosaic's, that is float4)
+    src = nodes[k + 1].piece
+    w, h = nodes[k].piece.roi_out.width, nodes[k].piece.roi_out.height
+    ow, oh = params.oriented_size(w, h, data.orientation)
+    fp = abi.Piece.make(w, h, channels=src.channels, processed_maximum=tuple(src.processed_maximum),
+                        roi_out=abi.Roi.make(0, 0, ow, oh))
+    out = list(nodes[:k + 1]) + [Node("flip", data, fp)]
+    for n in nodes[k + 1:]:
+        p = n.piece
+        q = abi.Piece.make(ow, oh, filters=p.filters, channels=p.channels, datatype=p.datatype,
+                           processed_maximum=tuple(p.processed_maximum))
+        out.append(Node(n.op, n.data, q))
+    return out
+
+
 def light_pipe_nodes(width, height, lut_target_ptr, lut_first, lut_coeffs, with_filmic=True, filmic=None,
-                     demosaic_method=abi.DT_HIP_DEMOSAIC_RCD):
+                     demosaic_method=abi.DT_HIP_DEMOSAIC_RCD, orientation=None, image_orientation=0):
     """config 2 of BASELINE.json: rawprepare -> temperature -> highlights(clip) -> demosaic ->
-    exposure -> colorin -> color calibration -> filmic -> colorout -> u16, module defaults."""
+    exposure -> colorin -> color calibration -> filmic -> colorout -> u16, module defaults.
+    orientation (None: no node): the flip module between demosaic and exposure (insert_flip())."""
     raw = abi.Piece.make(width, height, filters=synth.FILTERS_RGGB, channels=1, datatype=abi.DT_HIP_TYPE_UINT16)
     cfa1 = abi.Piece.make(width, height, filters=synth.FILTERS_RGGB, channels=1, processed_maximum=(1, 1, 1, 1))
     cfa2 = abi.Piece.make(width, height, filters=synth.FILTERS_RGGB, channels=1, processed_maximum=synth.WB_COEFFS)
@@ -52,14 +75,18 @@ def light_pipe_nodes(width, height, lut_target_ptr, lut_first, lut_coeffs, with_
     lt = [(lut_target_ptr, lut_first, lut_coeffs)] * 3
     nodes.append(Node("colorout", params.conversion(params.SRGB_OUT @ params.WORK_IN, lut_target=lt), rgb))
     nodes.append(Node("export_u16", None, rgb))
+    if orientation is not None:
+        nodes = insert_flip(nodes, "demosaic", orientation, image_orientation)
     return nodes
 
 
 def denoise_pipe_nodes(width, height, lut_target_ptr, lut_first, lut_coeffs, filmic=None,
-                       diffuse_preset="lens_deblur_soft", diffuse_iterations=2, with_nlmeans=False, with_bilat=None):
+                       diffuse_preset="lens_deblur_soft", diffuse_iterations=2, with_nlmeans=False, with_bilat=None,
+                       orientation=None, image_orientation=0):
     """config 3 of BASELINE.json, as far as it runs on device: the light pipe + denoise (profiled)
     wavelets after demosaic and diffuse-or-sharpen after color calibration, in the reference's module
-    order (src/develop/iop_order.c:196-232)."""
+    order (src/develop/iop_order.c:196-232).  orientation (None: no node): the flip module between
+    denoise (profiled) and exposure (insert_flip())."""
     nodes = light_pipe_nodes(width, height, lut_target_ptr, lut_first, lut_coeffs, with_filmic=filmic is not None,
                              filmic=filmic)
     rgb = abi.Piece.make(width, height, channels=4, processed_maximum=synth.WB_COEFFS)
@@ -77,6 +104,8 @@ def denoise_pipe_nodes(width, height, lut_target_ptr, lut_first, lut_coeffs, fil
                 if with_bilat is None or with_bilat:
                     out.append(Node("bilat", abi.BilatData.bilateral(), rgb))
                 out.append(Node("lab_to_rgb", abi.LabData.make(params.WORK_OUT), rgb))
+    if orientation is not None:
+        out = insert_flip(out, "denoiseprofile", orientation, image_orientation)
     return out
 
 

@@ -108,7 +108,8 @@ int dt_hip_default_process_tiling_ptp(int devid, const char *op, const dt_hip_pi
  * that is finalscale, whose modify_roi_in() (src/iop/finalscale.c:76-107) relates the regions.  dt_hip_plan_tiles_roi()
  * is the tile grid of :1100-1220, dt_hip_tile_rois_finalscale() the three regions of one tile (:1228-1300) -- both pure
  * functions -- and dt_hip_default_process_tiling_roi() the loop of :1222-1370.  Like the reference, every tile is
- * resampled as an image of its own (finalscale ignores the region origins, finalscale.c:124-129). */
+ * resampled as an image of its own (finalscale ignores the region origins, finalscale.c:124-129).  flip (orientation) is
+ * the other module it drives: dt_hip_tile_rois_flip(), declared with the module below. */
 typedef struct dt_hip_tile_plan_roi_t
 {
   int32_t width, height;     /* largest buffer of a tile (input or output) */
@@ -589,6 +590,49 @@ int dt_hip_iop_finalscale_process(int devid, const dt_hip_piece_t *piece, const 
 int dt_hip_iop_initialscale_process(int devid, const dt_hip_piece_t *piece, const dt_hip_finalscale_data_t *d,
                                   dt_hip_mem_t dev_in, dt_hip_mem_t dev_out);
 
+/* flip (orientation): process() / process_cl(), src/iop/flip.c, whose pixel loop is dt_imageio_flip_buffers()
+ * (src/common/imageio.c).  `orientation` holds the bits of dt_image_orientation_t: FLIP_Y = 1, FLIP_X = 2, SWAP_XY = 4
+ * (-1, "the image's orientation", is resolved by commit_params(): ansel_amd/params.py flip()).  Input pixel (row j,
+ * column i) of a W x H input goes to
+ *
+ *   j' = FLIP_Y ? H-1-j : j,   i' = FLIP_X ? W-1-i : i,   out(row, col) = SWAP_XY ? (i', j') : (j', i')
+ *
+ * so with SWAP_XY the output is W rows of H pixels.  The eight values (numpy of x[row, col]; EXIF: the Orientation tag
+ * a file carries that needs this value to display upright):
+ *
+ *   0  none                                    x                      EXIF 1
+ *   1  FLIP_Y          mirror vertically       x[::-1]                EXIF 4
+ *   2  FLIP_X          mirror horizontally     x[:, ::-1]             EXIF 2
+ *   3  FLIP_Y|FLIP_X   rotate 180              np.rot90(x, 2)         EXIF 3
+ *   4  SWAP_XY         transpose               x.T                    EXIF 5
+ *   5  SWAP|FLIP_Y     rotate 90 clockwise     np.rot90(x, -1)        EXIF 6
+ *   6  SWAP|FLIP_X     rotate 90 counter-cw    np.rot90(x, 1)         EXIF 8
+ *   7  SWAP|FLIP_Y|X   transverse              np.rot90(x, 2).T       EXIF 7
+ *
+ * A pure permutation of whole pixels: every output word is an input word.  piece->channels 1 (f32) or 4 (float4);
+ * roi_in is the input's size, roi_out must be its oriented size; out of place.  Orientation 0 copies. */
+typedef struct dt_hip_flip_data_t
+{
+  int32_t orientation;
+} dt_hip_flip_data_t;
+int dt_hip_iop_flip_process(int devid, const dt_hip_piece_t *piece, const dt_hip_flip_data_t *d, dt_hip_mem_t dev_in,
+                            dt_hip_mem_t dev_out);
+/* modify_roi_out() / modify_roi_in(): a region of the iw x ih input frame <-> the region of the oriented frame it
+ * becomes (sizes swapped under SWAP_XY, origin mirrored / swapped); the two are inverse to each other.  Scale is
+ * kept.  Pure functions, no device needed. */
+int dt_hip_iop_flip_modify_roi_out(const dt_hip_flip_data_t *d, int iw, int ih, const dt_hip_roi_t *roi_in, dt_hip_roi_t *roi_out);
+int dt_hip_iop_flip_modify_roi_in(const dt_hip_flip_data_t *d, int iw, int ih, const dt_hip_roi_t *roi_out, dt_hip_roi_t *roi_in);
+/* distort_transform() / distort_backtransform(): points_count (x, y) pairs in place, input <-> output coordinates of an
+ * iw x ih input; pixel (j, i) covers [i, i+1) x [j, j+1), so a mirror is x -> iw - x */
+int dt_hip_iop_flip_distort_transform(const dt_hip_flip_data_t *d, int iw, int ih, float *points, size_t points_count);
+int dt_hip_iop_flip_distort_backtransform(const dt_hip_flip_data_t *d, int iw, int ih, float *points, size_t points_count);
+/* one tile of dt_hip_plan_tiles_roi()'s grid for flip (the peer of dt_hip_tile_rois_finalscale()): no overlap, so
+ * oroi_full == oroi_good and iroi_full is its preimage; DT_HIP_TILE_EMPTY as there.  dt_hip_default_process_tiling_roi()
+ * takes op "flip" with a dt_hip_flip_data_t. */
+int dt_hip_tile_rois_flip(const dt_hip_tile_plan_roi_t *plan, const dt_hip_roi_t *roi_in, const dt_hip_roi_t *roi_out,
+                          const dt_hip_flip_data_t *d, int tx, int ty, dt_hip_roi_t *iroi_full, dt_hip_roi_t *oroi_full,
+                          dt_hip_roi_t *oroi_good);
+
 /* basebuffer: process(), src/iop/basebuffer.c:118-160 -- the first node of every pipe copies the region
  * roi_out of the full sensor buffer (host memory of the mipmap cache, iwidth x iheight pixels of bpp bytes,
  * unpadded rows) into the pipe's first cacheline.  On the device that is the frame's upload: one 2-D
@@ -710,7 +754,10 @@ int dt_hip_iop_detailmask_process(int devid, const dt_hip_piece_t *piece, const 
  * module-by-module chain.  `op` is the module's op name ("rawprepare", "temperature",
  * "highlights", "demosaic", "denoiseprofile", "exposure", "colorin", "channelmixerrgb", "diffuse",
  * "nlmeans", "filmicrgb", "colorout"), the colourspace glue "rgb_to_lab" / "lab_to_rgb", or
- * "export_u16" (data NULL) for the final float -> u16 of src/imageio/imageio_core.c:729. */
+ * "export_u16" (data NULL) for the final float -> u16 of src/imageio/imageio_core.c:729.
+ * "flip" (dt_hip_flip_data_t) is a node that changes the frame's geometry: the nodes after a swapping orientation
+ * carry the swapped size; it is never fused with its neighbours, and an orientation-0 node is dropped when added (the
+ * pipe launches and computes what it would without it; a "blend" right after it is refused, as flip has no blending). */
 typedef struct dt_hip_pipe_t dt_hip_pipe_t;
 dt_hip_pipe_t *dt_hip_pipe_new(int devid);
 void dt_hip_pipe_free(dt_hip_pipe_t *pipe);
@@ -795,7 +842,8 @@ int dt_hip_batch_set_writer(dt_hip_batch_t *batch, dt_hip_batch_writer_t writer,
  * band (nlmeans_core.c:264-313: the grid is a function of the frame size).  Blend nodes with uniform, parametric or
  * host-rendered form masks (form_mask = the FRAME's plane, whole on every band's device) are pointwise and run on the
  * band; local contrast's bilateral grid is relayed from band to band (relay_buf below).  Refused in band mode: the local
- * laplacian, finalscale / initialscale, blends with a mask blur or mask feathering. */
+ * laplacian, finalscale / initialscale, a flip node with a non-zero orientation (row bands of a transposed frame
+ * are columns of its input), blends with a mask blur or mask feathering. */
 #define DT_HIP_BAND_EXCHANGE 1
 typedef struct dt_hip_band_t
 {
