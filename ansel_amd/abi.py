@@ -247,6 +247,18 @@ class ExportRowsData(C.Structure):
     _fields_ = [("bpp", C.c_int32), ("layers", C.c_int32)]
 
 
+DT_HIP_JPEG_444 = 0  # Y 1x1
+DT_HIP_JPEG_422 = 1  # Y 2x1
+DT_HIP_JPEG_420 = 2  # Y 2x2 (jpeg_set_defaults)
+
+
+class JpegData(C.Structure):
+    """dt_hip_jpeg_data_t: the baseline JPEG encoder behind export_u8 (jpeg.hip); icc is host memory the call copies"""
+    _fields_ = [("quality", C.c_int32), ("subsampling", C.c_int32), ("optimize_coding", C.c_int32),
+                ("density_unit", C.c_int32), ("x_density", C.c_int32), ("y_density", C.c_int32),
+                ("capacity", C.c_uint64), ("icc", C.c_void_p), ("icc_bytes", C.c_uint64)]
+
+
 class Band(C.Structure):
     """dt_hip_band_t: a row band of a frame split over several devices"""
     _fields_ = [("row0", C.c_int32), ("rows", C.c_int32), ("halo_top", C.c_int32), ("halo_bottom", C.c_int32),

@@ -55,6 +55,7 @@ enum op_t
   OP_EXPORT_U8,
   OP_DETAILMASK,
   OP_FLIP, // changes the geometry (SWAP_XY): never inside a fused group
+  OP_EXPORT_JPEG, // the last node, behind export_u8: a file, not pixels
   OP_UNKNOWN
 };
 
@@ -89,6 +90,7 @@ const op_info_t k_ops[] = {
   { "export_u8", 0, 4 },
   { "detailmask", sizeof(dt_hip_detailmask_data_t), 16 },
   { "flip", sizeof(dt_hip_flip_data_t), 0 },
+  { "export_jpeg", sizeof(dt_hip_jpeg_data_t), 0 },
 };
 
 struct node_t
@@ -96,6 +98,7 @@ struct node_t
   op_t op;
   dt_hip_piece_t piece;
   std::vector<unsigned char> data;
+  std::vector<unsigned char> icc; // export_jpeg: the node's copy of the ICC profile its data pointed to
   template <typename T> const T *as() const { return reinterpret_cast<const T *>(data.data()); }
 };
 
@@ -121,6 +124,7 @@ size_t out_bytes(const node_t &n)
     case OP_EXPORT_U8: return px * 4;
     case OP_EXPORT_ROWS:
       return px * (size_t)n.as<dt_hip_export_rows_t>()->layers * (size_t)(n.as<dt_hip_export_rows_t>()->bpp / 8);
+    case OP_EXPORT_JPEG: return (size_t)n.as<dt_hip_jpeg_data_t>()->capacity;
     default: return px * 16;
   }
 }
@@ -153,6 +157,13 @@ int run_single(int devid, const node_t &n, dt_hip_mem_t in, dt_hip_mem_t out)
     case OP_EXPORT_ROWS:
       return dt_hip_export_pack_rows(devid, n.piece.roi_out.width, n.piece.roi_out.height, n.as<dt_hip_export_rows_t>()->bpp,
                                      n.as<dt_hip_export_rows_t>()->layers, in, out);
+    case OP_EXPORT_JPEG:
+    {
+      dt_hip_jpeg_data_t d = *n.as<dt_hip_jpeg_data_t>();
+      d.icc = n.icc.empty() ? nullptr : n.icc.data();
+      d.icc_bytes = n.icc.size();
+      return dt_hip_export_jpeg(devid, n.piece.roi_out.width, n.piece.roi_out.height, &d, in, out);
+    }
     default: return DT_HIP_INVALID_ARG;
   }
 }
@@ -355,6 +366,11 @@ int dt_hip_pipe_add_node(dt_hip_pipe_t *pipe, const char *op, const dt_hip_piece
   n.op = o;
   n.piece = *piece;
   if(data_size) n.data.assign((const unsigned char *)data, (const unsigned char *)data + data_size);
+  if(o == OP_EXPORT_JPEG)
+  {
+    const dt_hip_jpeg_data_t *j = (const dt_hip_jpeg_data_t *)data;
+    if(j->icc && j->icc_bytes) n.icc.assign((const unsigned char *)j->icc, (const unsigned char *)j->icc + j->icc_bytes);
+  }
   pipe->nodes.push_back(n);
   pipe->planned = false;
   return DT_HIP_SUCCESS;
@@ -378,6 +394,14 @@ int dt_hip_pipe_process(dt_hip_pipe_t *pipe, dt_hip_mem_t dev_in, dt_hip_mem_t d
 {
   if(!pipe || !dev_in || !dev_out) return DT_HIP_INVALID_ARG;
   if(pipe->nodes.empty()) return DT_HIP_SUCCESS;
+  // the encoder takes the 8-bit frame and makes a file: nothing can read its output
+  for(size_t k = 0; k < pipe->nodes.size(); k++)
+    if(pipe->nodes[k].op == OP_EXPORT_JPEG && (k + 1 != pipe->nodes.size() || k == 0 || pipe->nodes[k - 1].op != OP_EXPORT_U8))
+    {
+      set_last_error("pipe: 'export_jpeg' must be the last node, directly behind 'export_u8' (it is node %zu of %zu%s%s)",
+                     k + 1, pipe->nodes.size(), k ? ", behind " : "", k ? k_ops[pipe->nodes[k - 1].op].name : "");
+      return DT_HIP_INVALID_ARG;
+    }
   // flip passes its input format through: a consumer that reads another one would read past the flip's output
   for(size_t k = 0; k + 1 < pipe->nodes.size(); k++)
     if(pipe->nodes[k].op == OP_FLIP && pipe->nodes[k + 1].piece.channels != pipe->nodes[k].piece.channels)
@@ -627,6 +651,7 @@ int band_halo_rows(const node_t &n)
     case OP_DIFFUSE: return diffuse_halo_rows(&n.piece, n.as<dt_hip_diffuse_data_t>());
     case OP_NLMEANS: return nlmeans_halo_rows(&n.piece, n.as<dt_hip_nlmeans_data_t>());
     case OP_FLIP: return n.as<dt_hip_flip_data_t>()->orientation == 0 ? 0 : -1;
+    case OP_EXPORT_JPEG: return -1;
     default: return 0;
   }
 }
@@ -1006,6 +1031,13 @@ int dt_hip_pipe_band_begin(dt_hip_pipe_t *pipe, const dt_hip_band_t *band, dt_hi
   if(!pipe->planned) pipe->plan();
   const int devid = pipe->devid;
   const dt_hip_band_t &b = *band;
+  for(const node_t &n : pipe->nodes)
+    if(n.op == OP_EXPORT_JPEG)
+    {
+      // a file is not rows: the entropy-coded data of one band depends on every band before it
+      set_last_error("band mode: 'export_jpeg' encodes the whole frame and has no row-band implementation");
+      return DT_HIP_INVALID_ARG;
+    }
   for(const node_t &n : pipe->nodes)
     if(n.op == OP_FLIP)
     {
@@ -1773,7 +1805,8 @@ int dt_hip_default_process_tiling_ptp(int devid, const char *op, const dt_hip_pi
   n.op = OP_UNKNOWN;
   for(int k = 0; k < (int)OP_UNKNOWN; k++)
     if(!strcmp(op, k_ops[k].name)) n.op = (op_t)k;
-  if(n.op == OP_UNKNOWN || n.op == OP_BLEND || data_size != k_ops[n.op].data_size || (data_size && !data))
+  if(n.op == OP_UNKNOWN || n.op == OP_BLEND || n.op == OP_EXPORT_JPEG || data_size != k_ops[n.op].data_size
+     || (data_size && !data))
   {
     set_last_error("tiling: module '%s' cannot be tiled here", op);
     return DT_HIP_INVALID_ARG;

@@ -7,6 +7,7 @@ colorspaces.c); here they are derived analytically from the published primaries 
 functions, which is all a matrix profile is.
 """
 import math
+import ctypes as C
 
 import numpy as np
 
@@ -215,3 +216,31 @@ def flip(orientation=abi.ORIENTATION_NULL, image_orientation=0):
 def oriented_size(width, height, orientation):
     """the frame's size after the flip module"""
     return (height, width) if orientation & abi.ORIENTATION_SWAP_XY else (width, height)
+
+
+def jpeg(quality, icc=None, dpi=None):
+    """dt_hip_jpeg_data_t for an Ansel JPEG export at `quality` (write_image() of src/imageio/format/jpeg.c, the block
+    inherited from darktable): jpeg_set_quality(q, TRUE); Y sampling 1x1 above 92, 2x1 at 91-92, 2x2 (the libjpeg
+    default) at 90 and below; optimize_coding always.  Below 80 that block turns input smoothing on and below 50 the
+    fast integer DCT, above 95 the float DCT: the device encodes neither, so those qualities raise ValueError.  (The
+    mapping is recalled, not checked against the Ansel source: DESIGN.md section 4.6.)
+    icc: the output profile's bytes (APP2 chunks), kept alive by the returned struct.  dpi: None (JFIF density 0, 1, 1)
+    or dots per inch, one number or (x, y).  `capacity` is left 0: set it to the output buffer's size
+    (dt_hip_jpeg_bound())."""
+    q = int(quality)
+    if not 80 <= q <= 95:
+        raise ValueError("JPEG quality %d: the device encodes 80..95 (islow DCT, no smoothing)" % q)
+    ss = abi.DT_HIP_JPEG_444 if q > 92 else abi.DT_HIP_JPEG_422 if q > 90 else abi.DT_HIP_JPEG_420
+    d = abi.JpegData(quality=q, subsampling=ss, optimize_coding=1, density_unit=0, x_density=1, y_density=1)
+    if dpi is not None:
+        xd, yd = (dpi, dpi) if np.isscalar(dpi) else dpi
+        xd, yd = int(round(xd)), int(round(yd))
+        if not (0 < xd < 65536 and 0 < yd < 65536):
+            raise ValueError("dpi %r does not fit the JFIF header" % (dpi,))
+        d.density_unit, d.x_density, d.y_density = 1, xd, yd
+    if icc:
+        icc = bytes(icc)
+        d._icc = C.create_string_buffer(icc, len(icc))
+        d.icc = C.cast(d._icc, C.c_void_p)
+        d.icc_bytes = len(icc)
+    return d

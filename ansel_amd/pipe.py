@@ -19,6 +19,7 @@ MODULE_BPP = {
     "colorout": (16, 16), "export_u16": (16, 8), "rgb_to_lab": (16, 16), "lab_to_rgb": (16, 16), "nlmeans": (16, 16),
     "bilat": (16 + 16, 16),  # splat reads L, slice reads + writes the plane (48 B/px)
     "flip": (16, 16),
+    "export_u8": (16, 4), "export_jpeg": (4, 0),
 }
 
 
@@ -48,6 +49,23 @@ def insert_flip(nodes, after_op, orientation, image_orientation=0):
                            processed_maximum=tuple(p.processed_maximum))
         out.append(Node(n.op, n.data, q))
     return out
+
+
+def with_jpeg(nodes, jpeg_data):
+    """the node list with its trailing export_u16 swapped for export_u8 + export_jpeg (jpeg_data: params.jpeg() or an
+    abi.JpegData, its capacity set -- jpeg_bound()).  The node's output is the little-endian uint64 file length, then the
+    file.  The other nodes are shared with `nodes`."""
+    if not nodes or nodes[-1].op != "export_u16":
+        raise ValueError("with_jpeg: the node list does not end in export_u16")
+    last = nodes[-1]
+    w, h = last.piece.roi_out.width, last.piece.roi_out.height
+    return list(nodes[:-1]) + [Node("export_u8", None, last.piece),
+                               Node("export_jpeg", jpeg_data, abi.Piece.make(w, h, channels=4))]
+
+
+def jpeg_bound(width, height, jpeg_data):
+    """dt_hip_jpeg_bound(): a capacity the encoder's output always fits"""
+    return int(lib.load().dt_hip_jpeg_bound(width, height, C.byref(jpeg_data)))
 
 
 def light_pipe_nodes(width, height, lut_target_ptr, lut_first, lut_coeffs, with_filmic=True, filmic=None,

@@ -441,6 +441,33 @@ typedef struct dt_hip_export_rows_t
 int dt_hip_export_pack_rows(int devid, int width, int height, int bpp, int layers, dt_hip_mem_t dev_in,
                             dt_hip_mem_t dev_out);
 
+/* JPEG export: the baseline encoder of libjpeg(-turbo) that src/imageio/format/jpeg.c write_image() hands the
+ * export_u8 buffer to, on the device and byte for byte (ansel_amd/csrc/jpeg.hip).  dev_in_rgba8: width x height RGBA
+ * u8 pixels (alpha ignored).  dev_out receives a little-endian uint64 file length L, then the L bytes of a JFIF file
+ * (SOI, APP0, APP2 ICC_PROFILE chunks, DQT x 2, SOF0, DHT x 4, SOS, entropy-coded data, EOI).  If 8 + L exceeds
+ * `capacity` the length word is UINT64_MAX and nothing is written past `capacity`; the call does not wait for the
+ * device, so the caller reads the word.  dt_hip_jpeg_bound(): a capacity that always suffices (0 for refused
+ * settings).  Refused with DT_HIP_INVALID_ARG: width or height outside 1..65535, another subsampling, quality outside
+ * 1..100.  In a pipe: node "export_jpeg" (data dt_hip_jpeg_data_t), the last node, directly behind "export_u8"; its
+ * output is `capacity` bytes. */
+#define DT_HIP_JPEG_444 0 /* Y 1x1 */
+#define DT_HIP_JPEG_422 1 /* Y 2x1 */
+#define DT_HIP_JPEG_420 2 /* Y 2x2 (jpeg_set_defaults) */
+typedef struct dt_hip_jpeg_data_t
+{
+  int32_t quality;         /* 1..100: jpeg_set_quality(q, force_baseline = TRUE) -> the two DQT tables (host side) */
+  int32_t subsampling;     /* DT_HIP_JPEG_* */
+  int32_t optimize_coding; /* 0: Annex K tables, 1: two-pass optimal tables */
+  int32_t density_unit;    /* JFIF APP0; libjpeg default 0, 1, 1 */
+  int32_t x_density, y_density;
+  uint64_t capacity;  /* bytes of dev_out, the 8-byte length word included */
+  const void *icc;    /* host memory, may be NULL; copied by the call (and by dt_hip_pipe_add_node) */
+  uint64_t icc_bytes;
+} dt_hip_jpeg_data_t;
+size_t dt_hip_jpeg_bound(int width, int height, const dt_hip_jpeg_data_t *d); /* pure, no device */
+int dt_hip_export_jpeg(int devid, int width, int height, const dt_hip_jpeg_data_t *d, dt_hip_mem_t dev_in_rgba8,
+                       dt_hip_mem_t dev_out);
+
 /* diffuse or sharpen: process(), src/iop/diffuse.c:1155-1258 -> wavelets_process() (:978-1106),
  * decompose_2D_Bspline() (src/pixel/bspline.h:351-377), heat_PDE_diffusion() (diffuse.c:760-968).
  * The struct is dt_iop_diffuse_params_t (diffuse.c:76-105; commit_params memcpy's it, :133-138)
