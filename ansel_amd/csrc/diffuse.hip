@@ -30,7 +30,10 @@
 namespace ansel
 {
 // diffuse_bspline.hip: one a-trous B-spline analysis in -> (hf, lf) at dilation mult
-int bspline_launch_decompose(int devid, hipStream_t s, const float4 *in, float4 *hf, float4 *lf, int w, int h, int mult);
+int bspline_launch_decompose(int devid, hipStream_t s, const float4 *in, float4 *hf, float4 *lf, int w, int h, int mult,
+                             const unsigned *gate = nullptr);
+// ... on three-float planes (dilations 1 .. 16; in4: the module's float4 input, whose alpha words raise alpha_flag)
+int bspline_launch_decompose3(int devid, hipStream_t s, const void *in, bool in4, float *lf, int w, int h, int mult, unsigned *alpha_flag);
 #ifdef ANSEL_HIP_MEASURING
 // ... two scales (dilations mult and 2 mult, mult 1 or 4) in one pass: in -> low1, low2 (diffuse_bspline.hip; no faster)
 int bspline_launch_decompose2(int devid, hipStream_t s, const float4 *in, float4 *low1, float4 *low2, int w, int h, int mult);
@@ -75,6 +78,10 @@ struct pde_args
   float post_m[3][4];
   int approx_div;      // measuring builds only (ANSEL_HIP_PDE_APPROX_DIV): PDE_APPROX below
   int off;             // measuring builds only (ANSEL_HIP_PDE_OFF): parts of the strip kernel switched off, PDE_OFF below
+  // the module's two sequences (diffuse_run()): a strip launch leaves at once if *gate is up (gate_sense 1, the three-float
+  // sequence) or down (gate_sense 2, the float4 sequence behind it); gate == nullptr: it runs
+  const unsigned *gate;
+  int gate_sense;
 };
 
 // What would the north star's 1 ULP buy?  Measuring builds can run the strip kernel with every division as v_rcp, one
@@ -499,14 +506,56 @@ __device__ __forceinline__ void pde_dma_planes(const float4 *const p0, const flo
                  : "v"(voff), "s"(p0), "s"(p2), "s"(d0), "s"(d2)
                  : "memory");
 }
-template <bool HSUB, int MODE, bool DMA = false>
-__global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__restrict__ hf, const float4 *__restrict__ hsub,
-                                                         const float4 *__restrict__ lf,
-                                                         float4 *__restrict__ out, const pde_args a, const int final_pass,
-                                                         const unsigned char *__restrict__ mask, const int strip,
-                                                         const int strips_per_class)
+// The three-float planes' form (L3 below): global_load_lds_dwordx3, lane l's 12 bytes to LDS bytes dst + 16 l .. dst + 16 l + 11 --
+// measured on gfx950: the LDS stride of the 12-byte form is 16 bytes, the fourth word of a slot is left as it was
+// (tests/test_gpu_diffuse_three_float.py) -- so the landing zones keep 16-byte slots while 12 bytes a sample cross the memory
+// interface.  H0_4: the first plane is the module's float4 input, fetched by global_load_lds_dwordx4 at its own offset
+template <bool H0_4>
+__device__ __forceinline__ void pde_dma_planes3(const void *const p0, const void *const p1, const void *const p2, const unsigned voff0,
+                                                const unsigned voff, const unsigned d0, const unsigned d1, const unsigned d2)
 {
+  unsigned keep;
+  if constexpr(H0_4)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 4\n\ts_mov_b32 %0, m0\n\t"
+                 "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
+                 "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx3 %2, %4\n\t"
+                 "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx3 %2, %5\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff0), "v"(voff), "s"(p0), "s"(p1), "s"(p2), "s"(d0), "s"(d1), "s"(d2)
+                 : "memory");
+  else
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 4\n\ts_mov_b32 %0, m0\n\t"
+                 "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx3 %1, %2\n\t"
+                 "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx3 %1, %3\n\t"
+                 "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx3 %1, %4\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(p0), "s"(p1), "s"(p2), "s"(d0), "s"(d1), "s"(d2)
+                 : "memory");
+}
+// three floats a sample: the planes of the module's first sequence, and the squared-ratio ring's entries there
+struct pde_px3
+{
+  float x, y, z;
+};
+// The body of the strip kernels.  L3 = 0: float4 planes (diffuse_pde_strip).  L3 = 1 / 2 (HSUB and DMA only; diffuse_pde_strip3):
+// every plane holds THREE floats a pixel -- the fourth channel is +0 in all of them by the premise of the module's first sequence
+// (diffuse_run()), so a support's alpha is blank (alpha_is_blank()) and the output's alpha is the 0.0f the blank path writes --
+// except the first plane at L3 = 2 (the module's float4 input, scale 0 of the first iteration) and the output of the final pass
+// (the module's float4 output).  The ring holds 12 B entries, the landing zones 16 B slots of which the DMA fills 12
+// (pde_dma_planes3()); the samples enter the arithmetic as float4 with a constant +0 in .w, which the compiler folds away with
+// the channel's work.
+template <bool HSUB, int MODE, bool DMA, int L3>
+__device__ __forceinline__ void pde_strip_body(const float4 *__restrict__ hf, const float4 *__restrict__ hsub,
+                                               const float4 *__restrict__ lf, float4 *__restrict__ out, const pde_args &a,
+                                               const int final_pass, const unsigned char *__restrict__ mask, const int strip,
+                                               const int strips_per_class)
+{
+  static_assert(L3 == 0 || (HSUB && DMA), "three-float planes: the low-pass chain's LDS-DMA form only");
+  if(a.gate && ((*a.gate != 0u) == (a.gate_sense == 1))) return;
   extern __shared__ float4 r2s[]; // [PDE_RING][256 + 2 * mult]; slot x of a row = column clamp(seg - mult + x)
+  pde_px3 *const r2s3 = reinterpret_cast<pde_px3 *>(r2s); // L3: the ring's entries are three floats
   const int mult = a.mult;
   const int cls = blockIdx.y / strips_per_class, k0s = (blockIdx.y - cls * strips_per_class) * strip;
   const int n_cls = (a.height - cls + mult - 1) / mult; // rows of this class
@@ -528,13 +577,27 @@ __global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__rest
   constexpr int NPL = HSUB ? 3 : 2;
   const int lane = tx & 63, zw = 64 + 2 * mult;
   float4 *const zone = r2s + PDE_RING * tw + (tx >> 6) * NPL * zw;
+  // L3: [PDE_RING][tw] three-float ring entries, then per wave the landing zone, [3][zw] slots of 16 bytes as above
+  float4 *const zone3 = reinterpret_cast<float4 *>(reinterpret_cast<char *>(r2s) + (size_t)PDE_RING * tw * 12) + (tx >> 6) * 3 * zw;
   // the zone's LDS byte address (what M0 takes): the pointer in the LDS address space, not the low half of a generic one
   using lds_f4_ptr = __attribute__((address_space(3))) float4 *;
-  const unsigned zone_lds = DMA ? (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(__UINTPTR_TYPE__)(lds_f4_ptr)zone) : 0u;
+  const unsigned zone_lds = !DMA ? 0u : (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(__UINTPTR_TYPE__)(lds_f4_ptr)(
+                                           L3 ? zone3 : zone));
   const unsigned off_main = (unsigned)cols[0] * 16u, off_halo = (unsigned)clampi(col - mult + 64, 0, a.width - 1) * 16u;
   // send for support row v: every lane one sample per plane, the first 2 mult lanes the zone's last 2 mult slots as well
   auto dma_row = [&](const int v) {
     const size_t y = PDE_ROW(v);
+    if constexpr(L3 != 0)
+    {
+      const unsigned m3 = (unsigned)cols[0] * 12u, h3 = (unsigned)clampi(col - mult + 64, 0, a.width - 1) * 12u;
+      const unsigned p0 = (unsigned)zw * 16u, p1 = 2u * p0;
+      const void *const b0 = L3 == 2 ? (const void *)(hf + y) : (const void *)((const float *)hf + 3 * y);
+      const void *const b1 = (const float *)hsub + 3 * y, *const b2 = (const float *)lf + 3 * y;
+      pde_dma_planes3<L3 == 2>(b0, b1, b2, L3 == 2 ? off_main : m3, m3, zone_lds, zone_lds + p0, zone_lds + p1);
+      if(lane < 2 * mult)
+        pde_dma_planes3<L3 == 2>(b0, b1, b2, L3 == 2 ? off_halo : h3, h3, zone_lds + 1024u, zone_lds + p0 + 1024u, zone_lds + p1 + 1024u);
+      return;
+    }
     const unsigned pl = (unsigned)zw * 16u;
     pde_dma_planes<NPL>(hf + y, hsub + y, lf + y, off_main, zone_lds, zone_lds + pl, zone_lds + (NPL - 1) * pl);
     if(lane < 2 * mult)
@@ -548,6 +611,18 @@ __global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__rest
     bool have;
   } pending;
   pending.have = false;
+  // a pixel of the output: L3 writes three floats except in the final pass (the module's float4 output)
+  auto store = [&](const size_t i, const float4 o) {
+    if(final_pass) nt_store(out + i, o);
+    else if constexpr(L3 != 0)
+    {
+      float *const p3 = (float *)out + 3 * i;
+      p3[0] = o.x;
+      p3[1] = o.y;
+      p3[2] = o.z;
+    }
+    else out[i] = o;
+  };
   // fetch support row v into set `slot` and leave its squared ratios in ring row v % PDE_RING
   auto fetch_row = [&](const int v, auto slot_tag) {
     constexpr int SL = decltype(slot_tag)::value;
@@ -562,6 +637,21 @@ __global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__rest
     {
       // everything this wave sent for has landed (and the row step before's store has left)
       asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+      if constexpr(L3 != 0)
+      {
+        // (the fourth word of a slot is the input's alpha -- +0 by the sequence's premise, tested by its first launch -- or whatever
+        // the LDS held: never read)
+#pragma unroll
+        for(int jj = 0; jj < 3; jj++)
+        {
+          const int x = lane + jj * mult;
+          const float4 v0 = zone3[x], v1 = zone3[zw + x], v2 = zone3[2 * zw + x];
+          c[jj] = make_float4(v0.x, v0.y, v0.z, 0.0f);
+          low[jj] = make_float4(v1.x, v1.y, v1.z, 0.0f);
+          Lw[SL][jj] = make_float4(v2.x, v2.y, v2.z, 0.0f);
+        }
+      }
+      else
 #pragma unroll
       for(int jj = 0; jj < 3; jj++)
       {
@@ -601,6 +691,18 @@ __global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__rest
       return ratio2_rgb(h, l, blank ? 0.0f : ratio2(h.w, l.w), PDE_APPROX(a));
     };
     if(PDE_OFF(a, 4)) return;
+    if constexpr(L3 != 0)
+    {
+      pde_px3 *const ring3 = r2s3 + (v % PDE_RING) * tw;
+      auto put = [&](const int x, const float4 h, const float4 l) {
+        const float4 r = ratio2_rgb(h, l, 0.0f, PDE_APPROX(a));
+        ring3[x] = { r.x, r.y, r.z };
+      };
+      put(tx + mult, Hw[SL][1], Lw[SL][1]);
+      if(tx < mult) put(tx, Hw[SL][0], Lw[SL][0]);
+      if(tx >= 256 - mult) put(tx + 2 * mult, Hw[SL][2], Lw[SL][2]);
+      return;
+    }
     ring[tx + mult] = ratios(Hw[SL][1], Lw[SL][1]);
     if(tx < mult) ring[tx] = ratios(Hw[SL][0], Lw[SL][0]);
     if(tx >= 256 - mult) ring[tx + 2 * mult] = ratios(Hw[SL][2], Lw[SL][2]);
@@ -616,8 +718,7 @@ __global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__rest
       // the row step before's pixel leaves, then the fetch of the NEXT step's row: both in flight through all of this step's arithmetic
       if(pending.have)
       {
-        if(final_pass) nt_store(out + pending.idx, pending.o);
-        else out[pending.idx] = pending.o;
+        store(pending.idx, pending.o);
         pending.have = false;
       }
       if(kk + 1 < nrows) dma_row(kk + 3);
@@ -627,7 +728,7 @@ __global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__rest
     const float4 H4[9] = { Hw[S0][0], Hw[S0][1], Hw[S0][2], Hw[S1][0], Hw[S1][1], Hw[S1][2], Hw[S2][0], Hw[S2][1], Hw[S2][2] };
     const float4 L4[9] = { Lw[S0][0], Lw[S0][1], Lw[S0][2], Lw[S1][0], Lw[S1][1], Lw[S1][2], Lw[S2][0], Lw[S2][1], Lw[S2][2] };
     const int row = r_first + kk * mult;
-    const bool blank = alpha_is_blank(H4, L4);
+    const bool blank = L3 != 0 || alpha_is_blank(H4, L4);
     // the output of the row step before goes out HERE: every register of the fetched row has been read by now (the blank test
     // reads the last of them), so no wait for a fetch comes behind this store -- the compiler merges the counters of the two
     // paths of a branch conservatively, and a store in front of the first use of a fetched register made that use wait for
@@ -635,13 +736,27 @@ __global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__rest
     __builtin_amdgcn_sched_barrier(0);
     if(pending.have && !PDE_OFF(a, 8))
     {
-      if(final_pass) nt_store(out + pending.idx, pending.o);
-      else out[pending.idx] = pending.o;
+      store(pending.idx, pending.o);
       pending.have = false;
     }
     __builtin_amdgcn_sched_barrier(0);
     float4 energy = make_float4(0.f, 0.f, 0.f, 0.f);
     if(PDE_OFF(a, 4)) energy = make_float4(0.5f, 0.5f, 0.5f, 0.5f);
+    else if constexpr(L3 != 0)
+#pragma unroll
+    for(int ii = 0; ii < 3; ii++)
+    {
+      const pde_px3 *const ring = r2s3 + ((kk + ii) % PDE_RING) * tw + tx;
+#pragma unroll
+      for(int jj = 0; jj < 3; jj++)
+      {
+        const pde_px3 r = ring[jj * mult];
+        energy.x += r.x;
+        energy.y += r.y;
+        energy.z += r.z;
+      }
+      if(!WIDE_READS || ii >= 1) asm volatile("" : "+v"(energy.x), "+v"(energy.y), "+v"(energy.z) : : "memory");
+    }
     else
 #pragma unroll
     for(int ii = 0; ii < 3; ii++)
@@ -663,7 +778,7 @@ __global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__rest
     }
     const size_t idx = (size_t)row * a.width + col;
     float4 o;
-    if(mask && !mask[idx])
+    if(L3 == 0 && mask && !mask[idx])
     {
       // outside the luminance mask: "only copy input to output", diffuse.c:927-937
       const float4 h = H4[4], l = L4[4];
@@ -709,12 +824,27 @@ __global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__rest
     if(kk + 2 < nrows) row_step(std::integral_constant<int, 2>(), kk + 2);
   }
   if constexpr(DMA) asm volatile("s_waitcnt vmcnt(0)" : : : "memory"); // nothing of this wave's is on its way to an LDS it has left
-  if(pending.have)
-  {
-    if(final_pass) nt_store(out + pending.idx, pending.o);
-    else out[pending.idx] = pending.o;
-  }
+  if(pending.have) store(pending.idx, pending.o);
 #undef PDE_ROW
+}
+
+template <bool HSUB, int MODE, bool DMA = false>
+__global__ __launch_bounds__(256, 3) void diffuse_pde_strip(const float4 *__restrict__ hf, const float4 *__restrict__ hsub,
+                                                         const float4 *__restrict__ lf,
+                                                         float4 *__restrict__ out, const pde_args a, const int final_pass,
+                                                         const unsigned char *__restrict__ mask, const int strip,
+                                                         const int strips_per_class)
+{
+  pde_strip_body<HSUB, MODE, DMA, 0>(hf, hsub, lf, out, a, final_pass, mask, strip, strips_per_class);
+}
+// the module's first sequence (diffuse_run()): the low-pass chain by LDS-DMA on three-float planes; H0_4: the first plane is the
+// module's float4 input (scale 0 of the first iteration).  The final pass writes the float4 output; no luminance mask
+template <int MODE, bool H0_4>
+__global__ __launch_bounds__(256, 3) void diffuse_pde_strip3(const float4 *__restrict__ hf, const float4 *__restrict__ hsub,
+                                                          const float4 *__restrict__ lf, float4 *__restrict__ out, const pde_args a,
+                                                          const int final_pass, const int strip, const int strips_per_class)
+{
+  pde_strip_body<true, MODE, true, H0_4 ? 2 : 1>(hf, hsub, lf, out, a, final_pass, nullptr, strip, strips_per_class);
 }
 
 // ---- build_mask() + inpaint_mask(), diffuse.c:1106-1152, with the generators of src/iop/noise_generator.h:36-93 ----
@@ -842,6 +972,8 @@ int dt_hip_iop_diffuse_process(int devid, const dt_hip_piece_t *piece, const dt_
 
 namespace ansel
 {
+// dt_hip_test_diffuse_probe(): where the next calls report which sequence ran (tests only; nullptr: nowhere)
+static void *g_diffuse_probe = nullptr;
 
 // first_row: the frame row of the buffer's first row (a row band, pipe.cpp) -- it only enters the seeds of the
 // inpainting noise, which the reference derives from the pixel's index in the frame
@@ -919,6 +1051,26 @@ static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diff
 
   hipStream_t st = stream_of(devid);
   const float4 *src = (const float4 *)dev_in;
+  // Three-float planes (diffuse_pde_strip3, bspline_decompose_strip3): the fourth channel is +0 everywhere a pipe runs this module
+  // (colorin's matrix writes 0 x + 0 y + 0 z there), and with +0 in the input's alpha every plane of the module holds +0 there
+  // (the analysis of +0 is +0; a blank support updates to +0, alpha_is_blank()) and the output's alpha is +0.  Where the chain
+  // takes every pass by LDS-DMA, the module runs as TWO sequences over the same memory, with no host synchronisation: first
+  // every analysis and PDE launch on three-float planes -- 12 B a sample read and written instead of 16 -- whose first launch
+  // raises `alpha_flag` if an input alpha word is not +0 (-0 included) and whose later launches then leave at once, the final pass
+  // included (dev_out may be dev_in); then the float4 launches of the other configurations, each leaving at once unless the flag
+  // is up.  The modes without a three-float kernel, the luminance mask, the dilations above PDE_DMA_MAX_MULT and the stored-HF /
+  // per-row paths take the float4 launches alone.
+  const int mode0 = pde_mode_of(a);
+  const bool three = err == DT_HIP_SUCCESS && lf_chain && !no_dma && !(d->threshold > 0.0f) && (1 << (scales - 1)) <= PDE_DMA_MAX_MULT &&
+                     !(iterations == 1 && dev_in == dev_out) && !measuring_env("ANSEL_HIP_PDE_GENERIC") &&
+                     (mode0 == PDE_MODE_DEBLUR || mode0 == PDE_MODE_ISOTROPIC);
+  unsigned *alpha_flag = nullptr;
+  if(three)
+  {
+    alpha_flag = (unsigned *)dt_hip_alloc_device_buffer(devid, sizeof(unsigned));
+    if(!alpha_flag) err = DT_HIP_SYSMEM_ALLOCATION;
+    else if(hipMemsetAsync(alpha_flag, 0, sizeof(unsigned), st) != hipSuccess) err = DT_HIP_DEFAULT_ERROR;
+  }
   unsigned char *mask = nullptr;
   float4 *inpainted = nullptr;
   if(err == DT_HIP_SUCCESS && d->threshold > 0.0f)
@@ -937,6 +1089,12 @@ static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diff
       src = inpainted;
     }
   }
+  for(int seq = three ? 0 : 1; seq < 2 && err == DT_HIP_SUCCESS; seq++)
+  {
+  const bool p3 = seq == 0; // the three-float sequence
+  a.gate = alpha_flag;
+  a.gate_sense = p3 ? 1 : 2;
+  if(three) src = (const float4 *)dev_in; // (no luminance mask here: the input is the module's)
   for(int it = 0; err == DT_HIP_SUCCESS && it < iterations; it++)
   {
     // iteration ping-pong, diffuse.c:1223-1249 (tmp[0] = "temp2", tmp[1] = "temp1")
@@ -968,7 +1126,8 @@ static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diff
       }
 #endif
       float4 *low = chain ? hf[s] : lf[s % 2];
-      err = bspline_launch_decompose(devid, st, level, chain ? nullptr : hf[s], low, w, h, 1 << s);
+      if(p3) err = bspline_launch_decompose3(devid, st, level, it == 0 && s == 0, (float *)low, w, h, 1 << s, alpha_flag);
+      else err = bspline_launch_decompose(devid, st, level, chain ? nullptr : hf[s], low, w, h, 1 << s, alpha_flag);
       level = low;
       residual = low;
     }
@@ -1028,6 +1187,26 @@ static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diff
           const size_t ring_dma = ring + (size_t)4 * 3 * (64 + 2 * a.mult) * sizeof(float4);
 #define PDE_LAUNCH_DMA(MD) diffuse_pde_strip<true, MD, true><<<sgrid, 256, ring_dma, st>>>(h0, h1, cur, to, a, s == 0, mask, strip, spc)
           bool launched = false;
+          if(p3)
+          {
+            // three-float planes: 12 B ring entries, and per wave a landing zone of 3 x 16 B slots (pde_dma_planes3())
+            const bool h0_4 = it == 0 && s == 0;
+            const size_t lds3 = (size_t)PDE_RING * (256 + 2 * a.mult) * 12 + (size_t)4 * 3 * (64 + 2 * a.mult) * 16;
+            const int last = s == 0 && it == iterations - 1; // the module's float4 output
+#define PDE_LAUNCH3(MD, H4) diffuse_pde_strip3<MD, H4><<<sgrid, 256, lds3, st>>>(h0, h1, cur, to, a, last, strip, spc)
+            if(mode == PDE_MODE_DEBLUR)
+            {
+              if(h0_4) PDE_LAUNCH3(PDE_MODE_DEBLUR, true);
+              else PDE_LAUNCH3(PDE_MODE_DEBLUR, false);
+            }
+            else
+            {
+              if(h0_4) PDE_LAUNCH3(PDE_MODE_ISOTROPIC, true);
+              else PDE_LAUNCH3(PDE_MODE_ISOTROPIC, false);
+            }
+#undef PDE_LAUNCH3
+            launched = true;
+          }
 #define PDE_CASE(MD)                     \
   if(!launched && mode == (MD))          \
   {                                      \
@@ -1057,6 +1236,7 @@ static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diff
     }
     src = dst;
   }
+  }
   for(int s = 0; s < scales; s++)
     if(hf[s]) dt_hip_release_mem_object(hf[s]);
   for(int k = 0; k < 2; k++)
@@ -1065,12 +1245,29 @@ static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diff
     if(tmp[k]) dt_hip_release_mem_object(tmp[k]);
   }
   if(mask) dt_hip_release_mem_object(mask);
+  if(alpha_flag)
+  {
+    if(g_diffuse_probe && err == DT_HIP_SUCCESS && hipMemcpyAsync(g_diffuse_probe, alpha_flag, sizeof(unsigned), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      err = DT_HIP_DEFAULT_ERROR;
+    dt_hip_release_mem_object(alpha_flag);
+  }
+  else if(g_diffuse_probe && err == DT_HIP_SUCCESS && hipMemsetAsync(g_diffuse_probe, 0xff, sizeof(unsigned), st) != hipSuccess)
+    err = DT_HIP_DEFAULT_ERROR;
   return err;
 }
 
 } // namespace ansel
 
 extern "C" {
+
+// test hook: after each later call, the 4 bytes at device address `sink` say which sequence produced the output -- 0 the
+// three-float one (its alpha flag stayed down), 1 the float4 one behind it (the flag went up), 0xffffffff the float4 launches
+// alone (a configuration the three-float sequence does not cover).  sink == nullptr switches the report off
+int dt_hip_test_diffuse_probe(void *sink)
+{
+  ansel::g_diffuse_probe = sink;
+  return DT_HIP_SUCCESS;
+}
 
 // tiling_callback(), diffuse.c:585-610
 void dt_hip_iop_diffuse_tiling(const dt_hip_piece_t *piece, const dt_hip_diffuse_data_t *d, dt_hip_tiling_t *tiling)

@@ -108,8 +108,10 @@ template <int R, int T>
 __global__ __launch_bounds__(256) void bspline_decompose_strip(const float4 *__restrict__ in, float4 *__restrict__ hf,
                                                                float4 *__restrict__ lf, const int width, const int height,
                                                                const int mult, const int groups, const int strip,
-                                                               const int strips_per_class)
+                                                               const int strips_per_class, const unsigned *__restrict__ gate)
 {
+  // gate != nullptr: the module's second sequence (diffuse.hip diffuse_run()), which runs only if the three-float one raised it
+  if(gate && *gate == 0u) return;
   __shared__ float4 vert[2][(T + 4) * R + 2];
   const int bx = blockIdx.x;
   const int cls = blockIdx.y / strips_per_class, k0s = (blockIdx.y - cls * strips_per_class) * strip;
@@ -207,6 +209,133 @@ __global__ __launch_bounds__(256) void bspline_decompose_strip(const float4 *__r
 #undef BS_ROW
 }
 
+// The same analysis on THREE-FLOAT planes (12 B a sample, interleaved x y z): what the module's first sequence runs while the
+// fourth channel of its input is +0 everywhere (diffuse.hip diffuse_run()), the channel the taps then leave +0 -- 0.0625 (+0) +
+// ... = +0 and max_first(0, +0) = +0 -- and that is not stored.  R = mult adjacent columns x T = 256 / mult steps: a workgroup's
+// columns are one contiguous span of 256 (12 B x 64 lanes = 768 contiguous bytes a wave-instruction, where the float4 kernel's
+// R x 16 B pieces make one 128-byte line a step and 12 B x 8 would straddle lines).  IN4: the module's input, a float4 plane --
+// read whole and its alpha word tested: a lane that read one that is not +0 (-0 included) RAISES `alpha_flag`, and everything the
+// sequence launches after this leaves at once.  Not IN4: leaves at once if the flag is up.  Same taps, same order, same clipping,
+// same binary32 values in x y z.
+struct bs_px3
+{
+  float x, y, z;
+};
+__device__ __forceinline__ bs_px3 tap5(const bs_px3 a, const bs_px3 b, const bs_px3 c, const bs_px3 d, const bs_px3 e)
+{
+  return { tap5(a.x, b.x, c.x, d.x, e.x), tap5(a.y, b.y, c.y, d.y, e.y), tap5(a.z, b.z, c.z, d.z, e.z) };
+}
+template <int R, int T, bool IN4>
+__global__ __launch_bounds__(256) void bspline_decompose_strip3(const void *__restrict__ in_v, bs_px3 *__restrict__ lf,
+                                                                const int width, const int height, const int strip,
+                                                                const int strips_per_class, unsigned *__restrict__ alpha_flag)
+{
+  static_assert(R * T == 256, "a workgroup's columns: one span of 256");
+  constexpr int mult = R;
+  if(!IN4 && *alpha_flag != 0u) return;
+  __shared__ bs_px3 vert[2][(T + 4) * R + 2];
+  const float4 *const in4 = static_cast<const float4 *>(in_v);
+  const bs_px3 *const in3 = static_cast<const bs_px3 *>(in_v);
+  unsigned alpha_bits = 0; // IN4: the alpha words this lane read
+  auto at = [&](const size_t i) -> bs_px3 {
+    if constexpr(IN4)
+    {
+      const float4 v = in4[i];
+      alpha_bits |= __float_as_uint(v.w);
+      return { v.x, v.y, v.z };
+    }
+    else
+      return in3[i];
+  };
+  const int cls = blockIdx.y / strips_per_class, k0s = (blockIdx.y - cls * strips_per_class) * strip;
+  const int n_cls = (height - cls + mult - 1) / mult; // rows of this class
+  if(k0s >= n_cls) return;
+  const int nrows = (strip < n_cls - k0s) ? strip : n_cls - k0s;
+  const int r_first = cls + k0s * mult;
+  const int k0 = (int)blockIdx.x * T;
+  const int tid = threadIdx.x;
+  const int r = tid % R, k = tid / R;
+  const int col = r + (k0 + k) * mult;
+  const bool own = col < width;
+  int col2 = -1, slot2 = 0;
+  if(tid < 4 * R)
+  {
+    const int hr = tid % R, hs = tid / R;
+    const int hk = hs < 2 ? hs - 2 : T + hs - 2;
+    const int hcol = hr + (k0 + hk) * mult;
+    if(hcol >= 0 && hcol < width)
+    {
+      col2 = hcol;
+      slot2 = (hk + 2) * R + hr;
+    }
+  }
+  else if(tid == 4 * R)
+  {
+    col2 = 0;
+    slot2 = (T + 4) * R;
+  }
+  else if(tid == 4 * R + 1)
+  {
+    col2 = width - 1;
+    slot2 = (T + 4) * R + 1;
+  }
+  const bool second = col2 >= 0;
+#define BS_ROW(q) ((size_t)clampi(r_first + (q) * mult, 0, height - 1) * width)
+  const bs_px3 z = { 0.f, 0.f, 0.f };
+  bs_px3 a = z, b = z, c = z, d = z, e = z, a2 = z, b2 = z, c2 = z, d2 = z, e2 = z;
+  if(own)
+  {
+    a = at(BS_ROW(-2) + col);
+    b = at(BS_ROW(-1) + col);
+    c = at(BS_ROW(0) + col);
+    d = at(BS_ROW(1) + col);
+    e = at(BS_ROW(2) + col);
+  }
+  if(second)
+  {
+    a2 = at(BS_ROW(-2) + col2);
+    b2 = at(BS_ROW(-1) + col2);
+    c2 = at(BS_ROW(0) + col2);
+    d2 = at(BS_ROW(1) + col2);
+    e2 = at(BS_ROW(2) + col2);
+  }
+  for(int kk = 0; kk < nrows; kk++)
+  {
+    const int row = r_first + kk * mult;
+    const bool more = kk + 1 < nrows;
+    bs_px3 n1 = z, n2 = z;
+    if(more && own) n1 = at(BS_ROW(kk + 3) + col);
+    if(more && second) n2 = at(BS_ROW(kk + 3) + col2);
+    bs_px3 *const V = vert[kk & 1];
+    if(own) V[(k + 2) * R + r] = tap5(a, b, c, d, e);
+    if(second) V[slot2] = tap5(a2, b2, c2, d2, e2);
+    __syncthreads();
+    if(own)
+    {
+      bs_px3 t[5];
+#pragma unroll
+      for(int s = -2; s <= 2; s++)
+      {
+        const int cc = col + s * mult;
+        t[s + 2] = cc < 0 ? V[(T + 4) * R] : (cc > width - 1 ? V[(T + 4) * R + 1] : V[(k + s + 2) * R + r]);
+      }
+      lf[(size_t)row * width + col] = tap5(t[0], t[1], t[2], t[3], t[4]);
+    }
+    a = b;
+    b = c;
+    c = d;
+    d = e;
+    e = n1;
+    a2 = b2;
+    b2 = c2;
+    c2 = d2;
+    d2 = e2;
+    e2 = n2;
+  }
+#undef BS_ROW
+  // (every pixel of the frame is the centre sample `c` of the lane that owns its column in some row step)
+  if(IN4 && __builtin_amdgcn_ballot_w64(alpha_bits != 0u) != 0ull && (tid & 63) == 0) atomicOr(alpha_flag, 1u);
+}
 
 #ifdef ANSEL_HIP_MEASURING
 // MEASURING BUILD ONLY -- equal in time to the two single-scale launches it replaces (profiles/r04_negative_results.txt,
@@ -389,7 +518,32 @@ int bspline_launch_decompose2(int devid, hipStream_t s, const float4 *in, float4
 }
 #endif // ANSEL_HIP_MEASURING
 
-int bspline_launch_decompose(int devid, hipStream_t s, const float4 *in, float4 *hf, float4 *lf, int w, int h, int mult)
+// the three-float analysis (bspline_decompose_strip3): in (float4 if in4, else three floats a pixel) -> lf (three floats), at
+// dilation mult 1 .. 16; in4 raises alpha_flag, the others leave at once when it is up.  DT_HIP_INVALID_ARG for another form
+int bspline_launch_decompose3(int devid, hipStream_t s, const void *in, bool in4, float *lf, int w, int h, int mult, unsigned *alpha_flag)
+{
+  (void)devid;
+  if(mult != 1 && mult != 2 && mult != 4 && mult != 8 && mult != 16) return DT_HIP_INVALID_ARG;
+  if(in4 && mult != 1) return DT_HIP_INVALID_ARG;
+  const int classes = h < mult ? h : mult, per_class = (h + mult - 1) / mult;
+  const int gx = (w + 255) / 256; // a workgroup a span of 256 columns
+  int strip = 32;
+  while(strip > 4 && (size_t)gx * classes * ((per_class + strip - 1) / strip) < 2048) strip /= 2;
+  const int spc = (per_class + strip - 1) / strip;
+  const dim3 grid(gx, classes * spc);
+  launch_scope ls(devid, "diffuse_decompose");
+  bs_px3 *const out = reinterpret_cast<bs_px3 *>(lf);
+  if(in4) bspline_decompose_strip3<1, 256, true><<<grid, 256, 0, s>>>(in, out, w, h, strip, spc, alpha_flag);
+  else if(mult == 1) bspline_decompose_strip3<1, 256, false><<<grid, 256, 0, s>>>(in, out, w, h, strip, spc, alpha_flag);
+  else if(mult == 2) bspline_decompose_strip3<2, 128, false><<<grid, 256, 0, s>>>(in, out, w, h, strip, spc, alpha_flag);
+  else if(mult == 4) bspline_decompose_strip3<4, 64, false><<<grid, 256, 0, s>>>(in, out, w, h, strip, spc, alpha_flag);
+  else if(mult == 8) bspline_decompose_strip3<8, 32, false><<<grid, 256, 0, s>>>(in, out, w, h, strip, spc, alpha_flag);
+  else bspline_decompose_strip3<16, 16, false><<<grid, 256, 0, s>>>(in, out, w, h, strip, spc, alpha_flag);
+  return check_launch("diffuse_decompose");
+}
+
+int bspline_launch_decompose(int devid, hipStream_t s, const float4 *in, float4 *hf, float4 *lf, int w, int h, int mult,
+                             const unsigned *gate)
 {
   const int steps = (w + mult - 1) / mult; // steps of the dilation across a row
   launch_scope ls(devid, "diffuse_decompose");
@@ -419,10 +573,10 @@ int bspline_launch_decompose(int devid, hipStream_t s, const float4 *in, float4 
   while(strip > 4 && (size_t)gx * classes * ((per_class + strip - 1) / strip) < 2048) strip /= 2;
   const int spc = (per_class + strip - 1) / strip;
   const dim3 grid(gx, classes * spc);
-  if(mult == 1) bspline_decompose_strip<1, 256><<<grid, 256, 0, s>>>(in, hf, lf, w, h, mult, 1, strip, spc);
-  else if(mult == 2) bspline_decompose_strip<2, 128><<<grid, 256, 0, s>>>(in, hf, lf, w, h, mult, 1, strip, spc);
-  else if(mult == 4) bspline_decompose_strip<4, 64><<<grid, 256, 0, s>>>(in, hf, lf, w, h, mult, 1, strip, spc);
-  else bspline_decompose_strip<8, 32><<<grid, 256, 0, s>>>(in, hf, lf, w, h, mult, mult / 8, strip, spc);
+  if(mult == 1) bspline_decompose_strip<1, 256><<<grid, 256, 0, s>>>(in, hf, lf, w, h, mult, 1, strip, spc, gate);
+  else if(mult == 2) bspline_decompose_strip<2, 128><<<grid, 256, 0, s>>>(in, hf, lf, w, h, mult, 1, strip, spc, gate);
+  else if(mult == 4) bspline_decompose_strip<4, 64><<<grid, 256, 0, s>>>(in, hf, lf, w, h, mult, 1, strip, spc, gate);
+  else bspline_decompose_strip<8, 32><<<grid, 256, 0, s>>>(in, hf, lf, w, h, mult, mult / 8, strip, spc, gate);
   return check_launch("diffuse_decompose");
 }
 } // namespace ansel

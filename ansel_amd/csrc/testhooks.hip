@@ -83,3 +83,36 @@ int dt_hip_test_sqrt_core(int devid, const void *x, const void *y, void *o, size
 int dt_hip_test_zero_or_above_2m96(int devid, const void *x, const void *y, void *o, size_t n) { return devmath_launch<13>(devid, x, y, o, n); }
 int dt_hip_test_div_uniform(int devid, const void *x, const void *y, void *o, size_t n) { return devmath_launch<14>(devid, x, y, o, n); }
 }
+
+// ---- test hook: where global_load_lds_dwordx3 puts each lane's 12 bytes (diffuse.hip pde_dma_planes3()) ----
+// One wave.  LDS is filled with 0xdeadbeef, lane l then fetches the 12 bytes at src + 12 (63 - l) -- a per-lane source -- by
+// LDS-DMA with M0 = the array's base + `base` bytes, in the form of the diffuse PDE (M0 saved and restored, lgkmcnt(0) and
+// s_nop 4 first); the 2 KB of LDS go to dst.  tests/test_gpu_diffuse_three_float.py expects lane l's words at base + 16 l and the
+// fourth word of each 16-byte slot untouched (what gfx950 does with the 12-byte form).
+namespace
+{
+__global__ __launch_bounds__(64) void lds_dma_x3_test(const float *__restrict__ src, unsigned *__restrict__ dst, const unsigned base)
+{
+  __shared__ unsigned lds[512];
+  for(int i = threadIdx.x; i < 512; i += 64) lds[i] = 0xdeadbeefu;
+  __syncthreads();
+  using lds_u32_ptr = __attribute__((address_space(3))) unsigned *;
+  const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(__UINTPTR_TYPE__)(lds_u32_ptr)lds) + base;
+  const unsigned voff = (63u - threadIdx.x) * 12u;
+  unsigned keep;
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 4\n\ts_mov_b32 %0, m0\n\t"
+               "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx3 %1, %2\n\t"
+               "s_mov_b32 m0, %0\n\ts_waitcnt vmcnt(0)"
+               : "=&s"(keep)
+               : "v"(voff), "s"(src), "s"(m0v)
+               : "memory");
+  __syncthreads();
+  for(int i = threadIdx.x; i < 512; i += 64) dst[i] = lds[i];
+}
+} // namespace
+extern "C" int dt_hip_test_lds_dma_x3(int devid, const void *src, void *dst, unsigned base)
+{
+  if(!valid_device(devid) || !src || !dst || base % 4 != 0 || base + 1024 > 2048) return DT_HIP_INVALID_ARG;
+  lds_dma_x3_test<<<1, 64, 0, stream_of(devid)>>>((const float *)src, (unsigned *)dst, base);
+  return check_launch("lds_dma_x3_test");
+}
