@@ -259,6 +259,12 @@ class JpegData(C.Structure):
                 ("capacity", C.c_uint64), ("icc", C.c_void_p), ("icc_bytes", C.c_uint64)]
 
 
+class PngData(C.Structure):
+    """dt_hip_png_data_t: the PNG encoder behind export_u8 / export_u16 (png.hip); icc is host memory the call copies"""
+    _fields_ = [("bit_depth", C.c_int32), ("compression_level", C.c_int32), ("dpi", C.c_int32),
+                ("capacity", C.c_uint64), ("icc", C.c_void_p), ("icc_bytes", C.c_uint64)]
+
+
 class Band(C.Structure):
     """dt_hip_band_t: a row band of a frame split over several devices"""
     _fields_ = [("row0", C.c_int32), ("rows", C.c_int32), ("halo_top", C.c_int32), ("halo_bottom", C.c_int32),

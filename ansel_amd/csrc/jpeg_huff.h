@@ -9,6 +9,10 @@
 // minimum searches of a merge are the only work over all 257 symbols; each lane scans its share and the wave
 // reduces one key (count << 9 | 511 - symbol) with `wave_min`.  The bookkeeping of a merge is serial and runs on
 // lane 0 between two `sync()`s.
+//
+// jh_build() is that body with the alphabet, the length limit and the reserved pseudo-symbol as arguments: the PNG
+// encoder's deflate (png_deflate.h) builds its 286 / 30 / 19-symbol codes with it, limited to 15 / 15 / 7 bits and
+// without the pseudo-symbol, so that each code is complete as inflate requires (the K.3 moves keep the Kraft sum).
 #pragma once
 #include <stdint.h>
 
@@ -19,22 +23,23 @@
 #endif
 
 #define JH_NSYM 257
+#define JH_MAX_SYM 288 // the work arrays: JPEG's 256 symbols + 1, deflate's 286 literal / length symbols
 #define JH_MAX_CLEN 32
 
 struct jh_work_t
 {
-  int64_t freq[JH_NSYM]; // caller fills 0..255; 256 is set here
-  int32_t codesize[JH_NSYM];
-  int32_t others[JH_NSYM];
+  int64_t freq[JH_MAX_SYM]; // caller fills the real symbols; the pseudo-symbol is set here
+  int32_t codesize[JH_MAX_SYM];
+  int32_t others[JH_MAX_SYM];
   int32_t bits[JH_MAX_CLEN + 1];
   int32_t start[JH_MAX_CLEN + 2];
 };
 
 // the lane-local part of one minimum search: the smallest key among this lane's eligible symbols (~0: none)
-JH_FN uint64_t jh_local_min(const jh_work_t *w, int lane, int nlanes, int skip)
+JH_FN uint64_t jh_local_min(const jh_work_t *w, int nsym, int lane, int nlanes, int skip)
 {
   uint64_t k = ~0ull;
-  for(int i = lane; i < JH_NSYM; i += nlanes)
+  for(int i = lane; i < nsym; i += nlanes)
   {
     const int64_t f = w->freq[i];
     if(f != 0 && f <= 1000000000LL && i != skip)
@@ -46,25 +51,28 @@ JH_FN uint64_t jh_local_min(const jh_work_t *w, int lane, int nlanes, int skip)
   return k;
 }
 
-// bits_out[0..15]: the number of codes of length 1..16; vals_out: the symbols in code order; returns their count.
-// All lanes of the group call it; only lane 0 writes bits_out / vals_out.
-template <class WaveMin, class Sync>
-JH_FN int jh_gen_optimal_table(jh_work_t *w, int lane, int nlanes, WaveMin wave_min, Sync sync, uint8_t *bits_out,
-                               uint8_t *vals_out)
+// bits_out[0..limit-1]: the number of codes of length 1..limit; vals_out: the symbols in code order; returns their
+// count.  nreal symbols 0..nreal-1 (freq filled by the caller); reserve: the pseudo-symbol nreal with a count of 1,
+// whose code (the all-ones one) is dropped at the end.  All lanes of the group call it; only lane 0 writes bits_out /
+// vals_out.
+template <class V, class WaveMin, class Sync>
+JH_FN int jh_build(jh_work_t *w, int nreal, int limit, bool reserve, int lane, int nlanes, WaveMin wave_min, Sync sync,
+                   uint8_t *bits_out, V *vals_out)
 {
-  for(int i = lane; i < JH_NSYM; i += nlanes)
+  const int nsym = nreal + (reserve ? 1 : 0);
+  for(int i = lane; i < nsym; i += nlanes)
   {
     w->codesize[i] = 0;
     w->others[i] = -1;
   }
-  if(lane == 0) w->freq[256] = 1;
+  if(lane == 0 && reserve) w->freq[nreal] = 1;
   sync();
   for(;;)
   {
-    const uint64_t k1 = wave_min(jh_local_min(w, lane, nlanes, -1));
+    const uint64_t k1 = wave_min(jh_local_min(w, nsym, lane, nlanes, -1));
     if(k1 == ~0ull) break;
     int c1 = 511 - (int)(k1 & 511);
-    const uint64_t k2 = wave_min(jh_local_min(w, lane, nlanes, c1));
+    const uint64_t k2 = wave_min(jh_local_min(w, nsym, lane, nlanes, c1));
     if(k2 == ~0ull) break;
     int c2 = 511 - (int)(k2 & 511);
     sync();
@@ -92,23 +100,23 @@ JH_FN int jh_gen_optimal_table(jh_work_t *w, int lane, int nlanes, WaveMin wave_
   if(lane == 0)
   {
     for(int i = 0; i <= JH_MAX_CLEN; i++) w->bits[i] = 0;
-    for(int i = 0; i < JH_NSYM; i++)
+    for(int i = 0; i < nsym; i++)
     {
       int cs = w->codesize[i];
       if(cs > JH_MAX_CLEN) cs = JH_MAX_CLEN; // libjpeg stops with an error here; counts below 2^31 cannot get there
       w->codesize[i] = cs;
       if(cs) w->bits[cs]++;
     }
-    // the values' order: by unadjusted length, then value (256 excluded)
+    // the values' order: by unadjusted length, then value (the pseudo-symbol excluded)
     for(int i = 0; i <= JH_MAX_CLEN + 1; i++) w->start[i] = 0;
-    for(int j = 0; j < 256; j++)
+    for(int j = 0; j < nreal; j++)
       if(w->codesize[j]) w->start[w->codesize[j] + 1]++;
     for(int i = 1; i <= JH_MAX_CLEN + 1; i++) w->start[i] += w->start[i - 1];
-    for(int j = 0; j < 256; j++)
-      if(w->codesize[j]) vals_out[w->start[w->codesize[j]]++] = (uint8_t)j;
+    for(int j = 0; j < nreal; j++)
+      if(w->codesize[j]) vals_out[w->start[w->codesize[j]]++] = (V)j;
     nvals = w->start[JH_MAX_CLEN];
-    // Annex K.3: no code longer than 16 bits
-    for(int i = JH_MAX_CLEN; i > 16; i--)
+    // Annex K.3: no code longer than `limit` bits
+    for(int i = JH_MAX_CLEN; i > limit; i--)
     {
       while(w->bits[i] > 0)
       {
@@ -120,12 +128,23 @@ JH_FN int jh_gen_optimal_table(jh_work_t *w, int lane, int nlanes, WaveMin wave_
         w->bits[j]--;
       }
     }
-    int i = 16;
-    while(w->bits[i] == 0) i--;
-    w->bits[i]--; // the pseudo-symbol's code
-    for(int l = 1; l <= 16; l++) bits_out[l - 1] = (uint8_t)w->bits[l];
+    if(reserve)
+    {
+      int i = limit;
+      while(w->bits[i] == 0) i--;
+      w->bits[i]--; // the pseudo-symbol's code
+    }
+    for(int l = 1; l <= limit; l++) bits_out[l - 1] = (uint8_t)w->bits[l];
   }
   return nvals;
+}
+
+// JPEG: 256 symbols and the pseudo-symbol 256, codes of at most 16 bits
+template <class WaveMin, class Sync>
+JH_FN int jh_gen_optimal_table(jh_work_t *w, int lane, int nlanes, WaveMin wave_min, Sync sync, uint8_t *bits_out,
+                               uint8_t *vals_out)
+{
+  return jh_build(w, 256, 16, true, lane, nlanes, wave_min, sync, bits_out, vals_out);
 }
 
 // jchuff.c jpeg_make_c_derived_tbl(): code and length per symbol (length 0: no code)

@@ -56,6 +56,7 @@ enum op_t
   OP_DETAILMASK,
   OP_FLIP, // changes the geometry (SWAP_XY): never inside a fused group
   OP_EXPORT_JPEG, // the last node, behind export_u8: a file, not pixels
+  OP_EXPORT_PNG,  // the last node, behind export_u8 (8 bits) or export_u16 (16 bits): a file
   OP_UNKNOWN
 };
 
@@ -91,6 +92,7 @@ const op_info_t k_ops[] = {
   { "detailmask", sizeof(dt_hip_detailmask_data_t), 16 },
   { "flip", sizeof(dt_hip_flip_data_t), 0 },
   { "export_jpeg", sizeof(dt_hip_jpeg_data_t), 0 },
+  { "export_png", sizeof(dt_hip_png_data_t), 0 },
 };
 
 struct node_t
@@ -98,7 +100,7 @@ struct node_t
   op_t op;
   dt_hip_piece_t piece;
   std::vector<unsigned char> data;
-  std::vector<unsigned char> icc; // export_jpeg: the node's copy of the ICC profile its data pointed to
+  std::vector<unsigned char> icc; // export_jpeg / export_png: the node's copy of the ICC profile its data pointed to
   template <typename T> const T *as() const { return reinterpret_cast<const T *>(data.data()); }
 };
 
@@ -125,6 +127,7 @@ size_t out_bytes(const node_t &n)
     case OP_EXPORT_ROWS:
       return px * (size_t)n.as<dt_hip_export_rows_t>()->layers * (size_t)(n.as<dt_hip_export_rows_t>()->bpp / 8);
     case OP_EXPORT_JPEG: return (size_t)n.as<dt_hip_jpeg_data_t>()->capacity;
+    case OP_EXPORT_PNG: return (size_t)n.as<dt_hip_png_data_t>()->capacity;
     default: return px * 16;
   }
 }
@@ -163,6 +166,13 @@ int run_single(int devid, const node_t &n, dt_hip_mem_t in, dt_hip_mem_t out)
       d.icc = n.icc.empty() ? nullptr : n.icc.data();
       d.icc_bytes = n.icc.size();
       return dt_hip_export_jpeg(devid, n.piece.roi_out.width, n.piece.roi_out.height, &d, in, out);
+    }
+    case OP_EXPORT_PNG:
+    {
+      dt_hip_png_data_t d = *n.as<dt_hip_png_data_t>();
+      d.icc = n.icc.empty() ? nullptr : n.icc.data();
+      d.icc_bytes = n.icc.size();
+      return dt_hip_export_png(devid, n.piece.roi_out.width, n.piece.roi_out.height, &d, in, out);
     }
     default: return DT_HIP_INVALID_ARG;
   }
@@ -371,6 +381,11 @@ int dt_hip_pipe_add_node(dt_hip_pipe_t *pipe, const char *op, const dt_hip_piece
     const dt_hip_jpeg_data_t *j = (const dt_hip_jpeg_data_t *)data;
     if(j->icc && j->icc_bytes) n.icc.assign((const unsigned char *)j->icc, (const unsigned char *)j->icc + j->icc_bytes);
   }
+  if(o == OP_EXPORT_PNG)
+  {
+    const dt_hip_png_data_t *p = (const dt_hip_png_data_t *)data;
+    if(p->icc && p->icc_bytes) n.icc.assign((const unsigned char *)p->icc, (const unsigned char *)p->icc + p->icc_bytes);
+  }
   pipe->nodes.push_back(n);
   pipe->planned = false;
   return DT_HIP_SUCCESS;
@@ -401,6 +416,19 @@ int dt_hip_pipe_process(dt_hip_pipe_t *pipe, dt_hip_mem_t dev_in, dt_hip_mem_t d
       set_last_error("pipe: 'export_jpeg' must be the last node, directly behind 'export_u8' (it is node %zu of %zu%s%s)",
                      k + 1, pipe->nodes.size(), k ? ", behind " : "", k ? k_ops[pipe->nodes[k - 1].op].name : "");
       return DT_HIP_INVALID_ARG;
+    }
+  for(size_t k = 0; k < pipe->nodes.size(); k++)
+    if(pipe->nodes[k].op == OP_EXPORT_PNG)
+    {
+      const int depth = pipe->nodes[k].as<dt_hip_png_data_t>()->bit_depth;
+      const op_t want = depth == 16 ? OP_EXPORT_U16 : OP_EXPORT_U8;
+      if(k + 1 != pipe->nodes.size() || k == 0 || pipe->nodes[k - 1].op != want)
+      {
+        set_last_error("pipe: 'export_png' at %d bits must be the last node, directly behind '%s' (it is node %zu of %zu%s%s)",
+                       depth, k_ops[want].name, k + 1, pipe->nodes.size(), k ? ", behind " : "",
+                       k ? k_ops[pipe->nodes[k - 1].op].name : "");
+        return DT_HIP_INVALID_ARG;
+      }
     }
   // flip passes its input format through: a consumer that reads another one would read past the flip's output
   for(size_t k = 0; k + 1 < pipe->nodes.size(); k++)
@@ -652,6 +680,7 @@ int band_halo_rows(const node_t &n)
     case OP_NLMEANS: return nlmeans_halo_rows(&n.piece, n.as<dt_hip_nlmeans_data_t>());
     case OP_FLIP: return n.as<dt_hip_flip_data_t>()->orientation == 0 ? 0 : -1;
     case OP_EXPORT_JPEG: return -1;
+    case OP_EXPORT_PNG: return -1;
     default: return 0;
   }
 }
@@ -1036,6 +1065,13 @@ int dt_hip_pipe_band_begin(dt_hip_pipe_t *pipe, const dt_hip_band_t *band, dt_hi
     {
       // a file is not rows: the entropy-coded data of one band depends on every band before it
       set_last_error("band mode: 'export_jpeg' encodes the whole frame and has no row-band implementation");
+      return DT_HIP_INVALID_ARG;
+    }
+  for(const node_t &n : pipe->nodes)
+    if(n.op == OP_EXPORT_PNG)
+    {
+      // a file is not rows: the zlib stream of one band depends on every band before it
+      set_last_error("band mode: 'export_png' encodes the whole frame and has no row-band implementation");
       return DT_HIP_INVALID_ARG;
     }
   for(const node_t &n : pipe->nodes)
@@ -1805,7 +1841,7 @@ int dt_hip_default_process_tiling_ptp(int devid, const char *op, const dt_hip_pi
   n.op = OP_UNKNOWN;
   for(int k = 0; k < (int)OP_UNKNOWN; k++)
     if(!strcmp(op, k_ops[k].name)) n.op = (op_t)k;
-  if(n.op == OP_UNKNOWN || n.op == OP_BLEND || n.op == OP_EXPORT_JPEG || data_size != k_ops[n.op].data_size
+  if(n.op == OP_UNKNOWN || n.op == OP_BLEND || n.op == OP_EXPORT_JPEG || n.op == OP_EXPORT_PNG || data_size != k_ops[n.op].data_size
      || (data_size && !data))
   {
     set_last_error("tiling: module '%s' cannot be tiled here", op);

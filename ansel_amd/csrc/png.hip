@@ -1,0 +1,704 @@
+// png.hip -- PNG encoding of the export_u8 / export_u16 frame on gfx950: the file that Ansel's
+// src/imageio/format/png.c write_image() makes with libpng (RGB, 8 or 16 bits, no interlace), with libpng's filtered
+// stream byte for byte and a deflate of our own (png_deflate.h holds the body).
+//
+// Stages, all on the device's stream, no host synchronisation:
+//   png_filter   one workgroup per row: the five filters' sums (png_write_find_filter), the choice, the filtered row
+//   png_lz       one workgroup per segment of PD_SEG bytes: the Adler-32 partial sums; the matches (PD_NTAB hash
+//                tables in LDS, PD_STEP positions per step, atomicMax on insertion); the parse (wave 0 walks the match lengths
+//                of 64 positions at a time from registers); the symbol counts (an LDS histogram, integer atomics)
+//   png_tables   one wave per segment: the code lengths (jh_build(), limits 15 / 7), the block type
+//   png_scan     one workgroup: each segment's bit offset (a stored block's padding depends on where it starts: the
+//                offsets compose functions o -> o + L and o -> align8(o + a) + c), the Adler-32, L and whether it fits
+//   png_emit     one workgroup per segment: each thread's tokens' bits, a workgroup scan, integer OR on shared words
+//   png_tail     the zlib header and the Adler-32
+//   png_idat     one workgroup per IDAT chunk: the copy into the file and the chunk's CRC-32 (per-thread CRCs shifted
+//                by the bytes behind them and XORed)
+//   png_head     the host-built signature, IHDR, iCCP and pHYs; IEND
+// Nothing is written to dev_out past its capacity: the length word (the first 8 bytes) is L or UINT64_MAX, and the file
+// bytes are written only when they fit.
+#include <algorithm>
+#include <vector>
+
+#include "hip_common.h"
+#include "png_deflate.h"
+
+namespace ansel
+{
+namespace
+{
+
+constexpr int PT = 256;                    // threads per workgroup (png_tables: 64)
+constexpr int SEG_WORDS = PD_SEG / 64;     // 64-bit token masks per segment
+constexpr int SEG_PER_THREAD = PD_SEG / PT; // positions per thread in png_emit
+constexpr int NSYM = PD_NLIT + PD_NDIST;
+
+struct pstate_t
+{
+  uint64_t zbits;  // bit offset behind the last block (the zlib header included)
+  uint64_t zlen;   // bytes of the zlib stream
+  uint64_t nidat;  // IDAT chunks
+  uint64_t length; // L, or UINT64_MAX
+  uint32_t adler;
+  uint32_t fits;
+};
+
+template <class T>
+__device__ __forceinline__ T block_sum(T v)
+{
+  __shared__ T s[PT];
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for(int o = PT / 2; o > 0; o >>= 1)
+  {
+    if((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+    __syncthreads();
+  }
+  const T r = s[0];
+  __syncthreads();
+  return r;
+}
+
+__device__ __forceinline__ uint32_t block_xor(uint32_t v)
+{
+  __shared__ uint32_t s[PT];
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for(int o = PT / 2; o > 0; o >>= 1)
+  {
+    if((int)threadIdx.x < o) s[threadIdx.x] ^= s[threadIdx.x + o];
+    __syncthreads();
+  }
+  const uint32_t r = s[0];
+  __syncthreads();
+  return r;
+}
+
+template <class T>
+__device__ __forceinline__ T block_exclusive_scan(T v, T *total)
+{
+  __shared__ T s[PT];
+  const int t = threadIdx.x;
+  s[t] = v;
+  __syncthreads();
+  for(int o = 1; o < PT; o <<= 1)
+  {
+    const T a = t >= o ? s[t - o] : (T)0;
+    __syncthreads();
+    s[t] += a;
+    __syncthreads();
+  }
+  const T incl = s[t];
+  *total = s[PT - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+__global__ __launch_bounds__(PT) void png_filter(const void *__restrict__ in, const int w, const int depth,
+                                                 uint8_t *__restrict__ fs)
+{
+  const int y = blockIdx.x;
+  const uint32_t rb = (uint32_t)w * (depth == 8 ? 3 : 6);
+  uint64_t sum[5] = { 0, 0, 0, 0, 0 };
+  for(uint32_t j = threadIdx.x; j < rb; j += PT)
+  {
+    uint32_t r[5];
+    pf_byte(in, w, depth, y, j, r);
+#pragma unroll
+    for(int f = 0; f < 5; f++) sum[f] += pf_cost(r[f]);
+  }
+  uint64_t tot[5];
+#pragma unroll
+  for(int f = 0; f < 5; f++) tot[f] = block_sum<uint64_t>(sum[f]);
+  const int best = pf_choose(tot);
+  uint8_t *o = fs + (uint64_t)y * ((uint64_t)rb + 1);
+  if(threadIdx.x == 0) o[0] = (uint8_t)best;
+  for(uint32_t j = threadIdx.x; j < rb; j += PT)
+  {
+    uint32_t r[5];
+    pf_byte(in, w, depth, y, j, r);
+    o[1 + j] = (uint8_t)r[best];
+  }
+}
+
+// per segment: Adler-32 sums; at level > 0 the matches (m: len << 16 | dist - 1, at the positions that have one), the
+// parse (tokm: a token starts here, matm: that token is a match) and the symbol counts
+__global__ __launch_bounds__(PT) void png_lz(const uint8_t *__restrict__ fs, const uint64_t N, const int level,
+                                             uint32_t *__restrict__ m, uint64_t *__restrict__ tokm,
+                                             uint64_t *__restrict__ matm, uint32_t *__restrict__ freq,
+                                             pd_seg_t *__restrict__ segs)
+{
+  __shared__ int32_t head[PD_NTAB << PD_TBITS];
+  __shared__ uint8_t lenv[PD_SEG];
+  __shared__ uint64_t tk[SEG_WORDS], mt[SEG_WORDS];
+  __shared__ uint32_t hist[NSYM];
+  const int tid = threadIdx.x;
+  const uint64_t k = blockIdx.x;
+  const uint64_t s0 = k * PD_SEG, s1 = min(N, s0 + PD_SEG);
+  const uint32_t n = (uint32_t)(s1 - s0);
+  {
+    uint64_t S = 0, T = 0;
+    for(uint32_t j = tid; j < n; j += PT)
+    {
+      const uint32_t x = fs[s0 + j];
+      S += x;
+      T += (uint64_t)(n - j) * x;
+    }
+    S = block_sum<uint64_t>(S);
+    T = block_sum<uint64_t>(T);
+    if(tid == 0)
+    {
+      segs[k].adler_s = (uint32_t)(S % PD_ADLER_MOD);
+      segs[k].adler_t = (uint32_t)(T % PD_ADLER_MOD);
+    }
+  }
+  if(level == 0) return;
+  for(int i = tid; i < (PD_NTAB << PD_TBITS); i += PT) head[i] = -1;
+  for(int i = tid; i < PD_SEG; i += PT) lenv[i] = 0;
+  for(int i = tid; i < NSYM; i += PT) hist[i] = 0;
+  __syncthreads();
+  const uint64_t ws = s0 > PD_WIN ? s0 - PD_WIN : 0;
+  for(uint64_t c = ws; c < s1; c += PD_STEP)
+  {
+    const uint64_t p = c + tid;
+    if(p < s1 && p >= s0)
+    {
+      uint32_t dist;
+      const uint32_t l = pd_best(fs, N, p, ws, (uint32_t)min<uint64_t>(PD_MAXLEN, s1 - p),
+                                 [&](uint32_t slot) { return head[slot]; }, &dist);
+      if(l)
+      {
+        lenv[p - s0] = (uint8_t)(l - 2);
+        m[p] = (l << 16) | (dist - 1);
+      }
+    }
+    __syncthreads();
+    if(p < s1)
+      for(int t = 0; t < PD_NTAB && pd_keyed(p, N, t); t++) atomicMax(&head[pd_slot(fs, p, t)], (int32_t)(p - ws));
+    __syncthreads();
+  }
+  // the parse: wave 0, 64 positions' lengths per step in registers, the walk on the wave's uniform position
+  if(tid < 64)
+  {
+    const int lane = tid;
+    uint32_t s = 0;
+    for(uint32_t base = 0; base < n; base += 64)
+    {
+      const int lv = base + lane < n ? lenv[base + lane] : 0;
+      const int lv2 = base + 64 + lane < n ? lenv[base + 64 + lane] : 0;
+      uint64_t tkm = 0, mtm = 0;
+      while(s < base + 64 && s < n)
+      {
+        const int i = (int)(s - base);
+        const int lr = __builtin_amdgcn_readlane(lv, i);
+        const int lnr = i + 1 < 64 ? __builtin_amdgcn_readlane(lv, i + 1) : __builtin_amdgcn_readlane(lv2, 0);
+        const uint32_t l = lr ? lr + 2 : 0, ln = (s + 1 < n && lnr) ? lnr + 2 : 0;
+        tkm |= 1ull << i;
+        if(pd_take(l, ln, level))
+        {
+          mtm |= 1ull << i;
+          s += l;
+        }
+        else
+          s++;
+      }
+      if(lane == 0)
+      {
+        tk[base / 64] = tkm;
+        mt[base / 64] = mtm;
+      }
+    }
+  }
+  __syncthreads();
+  for(uint32_t j = tid; j < n; j += PT)
+  {
+    if(!((tk[j >> 6] >> (j & 63)) & 1)) continue;
+    if((mt[j >> 6] >> (j & 63)) & 1)
+    {
+      const uint32_t v = m[s0 + j];
+      uint32_t ne, ex;
+      atomicAdd(&hist[pd_len_sym(v >> 16, &ne, &ex)], 1u);
+      atomicAdd(&hist[PD_NLIT + pd_dist_sym((v & 0xffff) + 1, &ne, &ex)], 1u);
+    }
+    else
+      atomicAdd(&hist[fs[s0 + j]], 1u);
+  }
+  __syncthreads();
+  for(int i = tid; i < NSYM; i += PT) freq[k * NSYM + i] = hist[i] + (i == 256 ? 1u : 0u);
+  for(uint32_t i = tid; i < (n + 63) / 64; i += PT)
+  {
+    tokm[k * SEG_WORDS + i] = tk[i];
+    matm[k * SEG_WORDS + i] = mt[i];
+  }
+}
+
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
+{
+#pragma unroll
+  for(int o = 32; o > 0; o >>= 1)
+  {
+    const uint64_t other = __shfl_xor(v, o, 64);
+    v = other < v ? other : v;
+  }
+  return v;
+}
+
+// one wave per segment: code lengths and the block type (pd_tables)
+__global__ __launch_bounds__(64) void png_tables(const uint32_t *__restrict__ freq, const uint64_t N, const int level,
+                                                 pd_seg_t *__restrict__ segs)
+{
+  __shared__ pd_tab_work_t tw;
+  __shared__ uint32_t f[NSYM];
+  const uint64_t k = blockIdx.x;
+  const uint64_t s0 = k * PD_SEG;
+  const uint32_t n = (uint32_t)(min(N, s0 + PD_SEG) - s0);
+  if(level > 0)
+    for(int i = threadIdx.x; i < NSYM; i += 64) f[i] = freq[k * NSYM + i];
+  __syncthreads();
+  pd_tables(
+      &tw, f, n, level, threadIdx.x, 64, [](uint64_t v) { return wave_min_u64(v); }, []() { __syncthreads(); },
+      &segs[k]);
+}
+
+// the offset map of a run of segments: o -> o + c (align < 0) or o -> align8(o + a) + c
+struct omap_t
+{
+  int64_t a; // -1: no alignment
+  uint64_t c;
+};
+
+__device__ __forceinline__ omap_t omap_of(const pd_seg_t &s)
+{
+  if(s.type == PD_STORED) return { 3, 32 + 8 * (uint64_t)s.nbytes };
+  return { -1, s.bits };
+}
+
+__device__ __forceinline__ uint64_t align8(uint64_t v) { return (v + 7) & ~(uint64_t)7; }
+
+// f, then g
+__device__ __forceinline__ omap_t omap_then(omap_t f, omap_t g)
+{
+  if(g.a < 0) return { f.a, f.c + g.c };
+  if(f.a < 0) return { (int64_t)(g.a + f.c), g.c };
+  return { f.a, align8(f.c + (uint64_t)g.a) + g.c };
+}
+
+__device__ __forceinline__ uint64_t omap_apply(omap_t f, uint64_t o)
+{
+  return f.a < 0 ? o + f.c : align8(o + (uint64_t)f.a) + f.c;
+}
+
+// one workgroup: the segments' bit offsets, the Adler-32, the zlib length, L, whether it fits, the length word
+__global__ __launch_bounds__(PT) void png_scan(const pd_seg_t *__restrict__ segs, const uint64_t nseg, const uint64_t N,
+                                               const uint32_t head_len, const uint64_t capacity,
+                                               uint64_t *__restrict__ off, pstate_t *__restrict__ st,
+                                               uint8_t *__restrict__ out)
+{
+  __shared__ omap_t maps[PT];
+  __shared__ uint64_t starts[PT];
+  __shared__ uint64_t total;
+  const int t = threadIdx.x;
+  const uint64_t per = (nseg + PT - 1) / PT;
+  const uint64_t k0 = min(nseg, t * per), k1 = min(nseg, k0 + per);
+  omap_t f = { -1, 0 };
+  uint64_t A = 0, B = 0;
+  for(uint64_t k = k0; k < k1; k++)
+  {
+    const pd_seg_t &s = segs[k];
+    f = omap_then(f, omap_of(s));
+    const uint64_t e = min(N, (k + 1) * PD_SEG);
+    A += s.adler_s;
+    B = (B + s.adler_t + ((N - e) % PD_ADLER_MOD) * s.adler_s) % PD_ADLER_MOD;
+  }
+  maps[t] = f;
+  A = block_sum<uint64_t>(A % PD_ADLER_MOD);
+  B = block_sum<uint64_t>(B);
+  if(t == 0)
+  {
+    uint64_t o = 16; // the zlib header
+    for(int i = 0; i < PT; i++)
+    {
+      starts[i] = o;
+      o = omap_apply(maps[i], o);
+    }
+    total = o;
+  }
+  __syncthreads();
+  uint64_t o = starts[t];
+  for(uint64_t k = k0; k < k1; k++)
+  {
+    off[k] = o;
+    o = pd_seg_end(segs[k], o);
+  }
+  if(t == 0)
+  {
+    const uint32_t a = (uint32_t)((1 + A) % PD_ADLER_MOD), b = (uint32_t)((N % PD_ADLER_MOD + B) % PD_ADLER_MOD);
+    const uint64_t zlen = (total + 7) / 8 + 4;
+    const uint64_t nidat = (zlen + PD_IDAT - 1) / PD_IDAT;
+    const uint64_t L = head_len + zlen + 12 * nidat + 12;
+    const bool fits = 8 + L <= capacity;
+    st->zbits = total;
+    st->zlen = zlen;
+    st->nidat = nidat;
+    st->adler = (b << 16) | a;
+    st->fits = fits;
+    st->length = fits ? L : ~0ull;
+    for(int i = 0; i < 8; i++) out[i] = (uint8_t)(st->length >> (8 * i));
+  }
+}
+
+__global__ __launch_bounds__(PT) void png_zero(uint32_t *__restrict__ words, const pstate_t *__restrict__ st)
+{
+  const uint64_t n = (st->zlen + 3) / 4;
+  for(uint64_t i = blockIdx.x * (uint64_t)PT + threadIdx.x; i < n; i += (uint64_t)gridDim.x * PT) words[i] = 0;
+}
+
+__device__ __forceinline__ void or_byte(uint32_t *words, uint64_t i, uint32_t v)
+{
+  atomicOr(&words[i >> 2], (v & 255) << (8 * (i & 3)));
+}
+
+// nb (<= 25) bits at bit offset o, LSB first
+__device__ __forceinline__ void or_bits(uint32_t *words, uint64_t o, uint32_t v, int nb)
+{
+  const uint64_t x = (uint64_t)v << (o & 31);
+  atomicOr(&words[o >> 5], (uint32_t)x);
+  if((o & 31) + nb > 32) atomicOr(&words[(o >> 5) + 1], (uint32_t)(x >> 32));
+}
+
+// LSB-first writer from bit `start`: the first and the last word it touches are ORed, the words between stored
+struct writer_t
+{
+  uint32_t *words;
+  uint64_t acc;
+  int nacc;
+  uint64_t wi;
+  bool first;
+  __device__ writer_t(uint32_t *w, uint64_t start) : words(w), acc(0), nacc((int)(start & 31)), wi(start >> 5), first(true) {}
+  __device__ __forceinline__ void put(uint32_t v, int nb)
+  {
+    acc |= (uint64_t)v << nacc;
+    nacc += nb;
+    if(nacc >= 32)
+    {
+      if(first)
+        atomicOr(&words[wi], (uint32_t)acc);
+      else
+        words[wi] = (uint32_t)acc;
+      first = false;
+      wi++;
+      acc >>= 32;
+      nacc -= 32;
+    }
+  }
+  __device__ __forceinline__ void flush()
+  {
+    if(nacc > 0) atomicOr(&words[wi], (uint32_t)acc);
+  }
+};
+
+__global__ __launch_bounds__(PT) void png_emit(const uint8_t *__restrict__ fs, const uint32_t *__restrict__ m,
+                                               const uint64_t *__restrict__ tokm, const uint64_t *__restrict__ matm,
+                                               const pd_seg_t *__restrict__ segs, const uint64_t *__restrict__ off,
+                                               const uint64_t nseg, uint32_t *__restrict__ words)
+{
+  __shared__ pd_seg_t sg;
+  __shared__ uint16_t code[NSYM], cl_code[PD_NCL];
+  const int tid = threadIdx.x;
+  const uint64_t k = blockIdx.x;
+  const uint64_t s0 = k * PD_SEG;
+  const uint64_t o = off[k];
+  const bool last = k + 1 == nseg;
+  if(tid == 0)
+  {
+    sg = segs[k];
+    if(sg.type != PD_STORED)
+    {
+      pd_codes(sg.len, PD_NLIT, code, sg.type == PD_FIXED);
+      pd_codes(sg.len + PD_NLIT, PD_NDIST, code + PD_NLIT);
+      pd_codes(sg.cl_len, PD_NCL, cl_code);
+    }
+  }
+  __syncthreads();
+  const uint32_t n = sg.nbytes;
+  if(sg.type == PD_STORED)
+  {
+    const uint64_t q = align8(o + 3) / 8;
+    if(tid == 0)
+    {
+      or_bits(words, o, last ? 1u : 0u, 3);
+      or_byte(words, q, n & 255);
+      or_byte(words, q + 1, (n >> 8) & 255);
+      or_byte(words, q + 2, ~n & 255);
+      or_byte(words, q + 3, (~n >> 8) & 255);
+    }
+    for(uint32_t j = tid; j < n; j += PT) or_byte(words, q + 4 + j, fs[s0 + j]);
+    return;
+  }
+  const uint32_t j0 = min(n, (uint32_t)tid * SEG_PER_THREAD), j1 = min(n, j0 + SEG_PER_THREAD);
+  const uint64_t *tkw = tokm + k * SEG_WORDS, *mtw = matm + k * SEG_WORDS;
+  // each token of the thread's range: f(code, its length, extra, extra bits) for its one or two symbols
+  auto walk = [&](auto f) {
+    for(uint32_t j = j0; j < j1; j++)
+    {
+      if(!((tkw[j >> 6] >> (j & 63)) & 1)) continue;
+      if(!((mtw[j >> 6] >> (j & 63)) & 1))
+      {
+        const uint32_t b = fs[s0 + j];
+        f(code[b], sg.len[b], 0u, 0);
+        continue;
+      }
+      const uint32_t v = m[s0 + j];
+      uint32_t ne, ex;
+      const uint32_t ls = pd_len_sym(v >> 16, &ne, &ex);
+      f(code[ls], sg.len[ls], ex, (int)ne);
+      const uint32_t ds = pd_dist_sym((v & 0xffff) + 1, &ne, &ex);
+      f(code[PD_NLIT + ds], sg.len[PD_NLIT + ds], ex, (int)ne);
+    }
+  };
+  uint64_t nbits = 0;
+  walk([&](uint32_t, int l, uint32_t, int ne) { nbits += l + ne; });
+  if(tid == 0) pd_block_header(sg, last, cl_code, [&](uint32_t, int nb) { nbits += nb; });
+  if(tid == PT - 1) nbits += sg.len[256];
+  uint64_t total;
+  const uint64_t ex = block_exclusive_scan<uint64_t>(nbits, &total);
+  writer_t wr(words, o + ex);
+  if(tid == 0) pd_block_header(sg, last, cl_code, [&](uint32_t v, int nb) { wr.put(v, nb); });
+  walk([&](uint32_t c, int l, uint32_t e, int ne) {
+    wr.put(c, l);
+    if(ne) wr.put(e, ne);
+  });
+  if(tid == PT - 1) wr.put(code[256], sg.len[256]);
+  wr.flush();
+}
+
+// the zlib header and the Adler-32 behind the last block
+__global__ void png_tail(uint32_t *__restrict__ words, const uint32_t zheader, const pstate_t *__restrict__ st)
+{
+  if(threadIdx.x != 0) return;
+  or_byte(words, 0, zheader >> 8);
+  or_byte(words, 1, zheader & 255);
+  const uint64_t a = (st->zbits + 7) / 8;
+  for(int i = 0; i < 4; i++) or_byte(words, a + i, st->adler >> (24 - 8 * i));
+}
+
+constexpr int IDAT_PER_THREAD = PD_IDAT / PT;
+
+// one workgroup per IDAT chunk: length, type, the data copied from the zlib stream, CRC-32
+__global__ __launch_bounds__(PT) void png_idat(const uint8_t *__restrict__ z, const pstate_t *__restrict__ stp,
+                                               const uint32_t head_len, const uint32_t crc_type,
+                                               uint8_t *__restrict__ out)
+{
+  __shared__ uint32_t table[256];
+  const pstate_t st = *stp;
+  if(!st.fits) return;
+  {
+    uint32_t c = threadIdx.x;
+    for(int k = 0; k < 8; k++) c = c & 1 ? (c >> 1) ^ 0xedb88320u : c >> 1;
+    table[threadIdx.x] = c;
+  }
+  __syncthreads();
+  for(uint64_t ci = blockIdx.x; ci < st.nidat; ci += gridDim.x)
+  {
+    const uint64_t d0 = ci * PD_IDAT;
+    const uint32_t len = (uint32_t)min<uint64_t>(PD_IDAT, st.zlen - d0);
+    uint8_t *dst = out + 8 + head_len + ci * (PD_IDAT + 12);
+    const uint32_t p0 = min(len, (uint32_t)threadIdx.x * IDAT_PER_THREAD), p1 = min(len, p0 + IDAT_PER_THREAD);
+    uint32_t c = 0xffffffffu;
+    for(uint32_t j = p0; j < p1; j++)
+    {
+      const uint32_t b = z[d0 + j];
+      dst[8 + j] = (uint8_t)b;
+      c = table[(c ^ b) & 255] ^ (c >> 8);
+    }
+    c = ~c;
+    const uint32_t mine = p1 > p0 ? pd_multmodp(pd_x8n(len - p1), c) : 0u;
+    const uint32_t crc = block_xor(mine) ^ pd_multmodp(pd_x8n(len), crc_type);
+    if(threadIdx.x == 0)
+    {
+      const uint8_t hdr[8] = { (uint8_t)(len >> 24), (uint8_t)(len >> 16), (uint8_t)(len >> 8), (uint8_t)len,
+                               'I', 'D', 'A', 'T' };
+      for(int i = 0; i < 8; i++) dst[i] = hdr[i];
+      for(int i = 0; i < 4; i++) dst[8 + len + i] = (uint8_t)(crc >> (24 - 8 * i));
+    }
+  }
+}
+
+// the bytes in front of the first IDAT (host-built) and IEND
+__global__ __launch_bounds__(PT) void png_head(const uint8_t *__restrict__ head, const uint32_t head_len,
+                                               const pstate_t *__restrict__ stp, uint8_t *__restrict__ out)
+{
+  const pstate_t st = *stp;
+  if(!st.fits) return;
+  for(uint32_t i = threadIdx.x; i < head_len; i += PT) out[8 + i] = head[i];
+  if(threadIdx.x == 0)
+  {
+    const uint8_t iend[12] = { 0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82 };
+    for(int i = 0; i < 12; i++) out[8 + st.length - 12 + i] = iend[i];
+  }
+}
+
+// the frame's sizes; false (with the reason) for refused settings or a bound beyond size_t
+struct pgeom_t
+{
+  uint64_t N;     // filtered stream bytes
+  uint64_t nseg;
+  uint64_t zmax;  // the zlib stream's bytes at most
+  uint64_t head;  // bytes in front of the first IDAT
+  uint64_t bound; // 8 + the file at most
+};
+
+bool png_geometry(int width, int height, const dt_hip_png_data_t *d, const char *who, pgeom_t *g)
+{
+  if(!d)
+  {
+    set_last_error("%s: no dt_hip_png_data_t", who);
+    return false;
+  }
+  if(width < 1 || height < 1)
+  {
+    set_last_error("%s: %d x %d is not a frame", who, width, height);
+    return false;
+  }
+  if(d->bit_depth != 8 && d->bit_depth != 16)
+  {
+    set_last_error("%s: bit depth %d is not 8 or 16", who, (int)d->bit_depth);
+    return false;
+  }
+  if(d->compression_level < 0 || d->compression_level > 9)
+  {
+    set_last_error("%s: compression level %d is outside 0..9", who, (int)d->compression_level);
+    return false;
+  }
+  if(d->dpi < 0)
+  {
+    set_last_error("%s: dpi %d is negative", who, (int)d->dpi);
+    return false;
+  }
+  if(d->icc_bytes && !d->icc)
+  {
+    set_last_error("%s: icc_bytes %llu without an icc pointer", who, (unsigned long long)d->icc_bytes);
+    return false;
+  }
+  if(d->icc && d->icc_bytes > (1ull << 30))
+  {
+    set_last_error("%s: an ICC profile of %llu bytes does not fit an iCCP chunk", who, (unsigned long long)d->icc_bytes);
+    return false;
+  }
+  const unsigned __int128 rb = (unsigned __int128)width * (d->bit_depth / 8 * 3);
+  const unsigned __int128 N = (unsigned __int128)height * (rb + 1);
+  const unsigned __int128 nseg = (N + PD_SEG - 1) / PD_SEG;
+  const unsigned __int128 zmax = (42 * nseg + 8 * N + 7) / 8 + 6;
+  const unsigned __int128 head = 8 + 25 + pd_iccp_bytes(d->icc ? d->icc_bytes : 0) + (d->dpi > 0 ? 21 : 0);
+  const unsigned __int128 bound = 8 + head + zmax + 12 * ((zmax + PD_IDAT - 1) / PD_IDAT) + 12;
+  if(rb >= 0xffffffffu || nseg > 0x7fffffff || bound > (unsigned __int128)SIZE_MAX)
+  {
+    set_last_error("%s: the bound of a %d x %d frame at %d bits does not fit", who, width, height, (int)d->bit_depth);
+    return false;
+  }
+  g->N = (uint64_t)N;
+  g->nseg = (uint64_t)nseg;
+  g->zmax = (uint64_t)zmax;
+  g->head = (uint64_t)head;
+  g->bound = (uint64_t)bound;
+  return true;
+}
+
+} // namespace
+} // namespace ansel
+
+using namespace ansel;
+
+extern "C" size_t dt_hip_png_bound(int width, int height, const dt_hip_png_data_t *d)
+{
+  pgeom_t g;
+  if(!png_geometry(width, height, d, "dt_hip_png_bound", &g)) return 0;
+  return (size_t)g.bound;
+}
+
+extern "C" int dt_hip_export_png(int devid, int width, int height, const dt_hip_png_data_t *d, dt_hip_mem_t dev_in,
+                                 dt_hip_mem_t dev_out)
+{
+  if(!valid_device(devid) || !dev_in || !dev_out) return DT_HIP_INVALID_ARG;
+  pgeom_t g;
+  if(!png_geometry(width, height, d, "export_png", &g)) return DT_HIP_INVALID_ARG;
+  if(d->capacity < 8)
+  {
+    set_last_error("export_png: capacity %llu cannot hold the 8-byte length word", (unsigned long long)d->capacity);
+    return DT_HIP_INVALID_ARG;
+  }
+  const int level = d->compression_level;
+  const std::vector<uint8_t> head = pd_file_head(width, height, d->bit_depth, (const uint8_t *)d->icc,
+                                                 d->icc ? (size_t)d->icc_bytes : 0, d->dpi);
+  const uint32_t crc_type = pd_crc((const uint8_t *)"IDAT", 4);
+  const uint64_t N = g.N, nseg = g.nseg;
+  const uint64_t nwords = g.zmax / 4 + 2;
+  const uint64_t max_idat = (g.zmax + PD_IDAT - 1) / PD_IDAT;
+  // scratch from the runtime's pool, released behind the launches (the pool's reuse is stream-ordered)
+  const size_t sz_fs = (size_t)N, sz_m = level ? (size_t)N * 4 : 4, sz_tok = level ? (size_t)nseg * SEG_WORDS * 8 : 8;
+  const size_t sz_freq = (size_t)nseg * NSYM * 4, sz_segs = (size_t)nseg * sizeof(pd_seg_t), sz_off = (size_t)nseg * 8;
+  const size_t sz_words = (size_t)nwords * 4;
+  dt_hip_mem_t m_fs = dt_hip_alloc_device_buffer(devid, sz_fs);
+  dt_hip_mem_t m_m = dt_hip_alloc_device_buffer(devid, sz_m);
+  dt_hip_mem_t m_tok = dt_hip_alloc_device_buffer(devid, sz_tok);
+  dt_hip_mem_t m_mat = dt_hip_alloc_device_buffer(devid, sz_tok);
+  dt_hip_mem_t m_freq = dt_hip_alloc_device_buffer(devid, sz_freq);
+  dt_hip_mem_t m_segs = dt_hip_alloc_device_buffer(devid, sz_segs);
+  dt_hip_mem_t m_off = dt_hip_alloc_device_buffer(devid, sz_off);
+  dt_hip_mem_t m_words = dt_hip_alloc_device_buffer(devid, sz_words);
+  dt_hip_mem_t m_st = dt_hip_alloc_device_buffer(devid, sizeof(pstate_t));
+  dt_hip_mem_t m_head = dt_hip_alloc_device_buffer(devid, head.size());
+  auto release = [&]() {
+    for(dt_hip_mem_t x : { m_fs, m_m, m_tok, m_mat, m_freq, m_segs, m_off, m_words, m_st, m_head })
+      dt_hip_release_mem_object(x);
+  };
+  if(!m_fs || !m_m || !m_tok || !m_mat || !m_freq || !m_segs || !m_off || !m_words || !m_st || !m_head)
+  {
+    release();
+    return DT_HIP_DEFAULT_ERROR;
+  }
+  hipStream_t s = stream_of(devid);
+  int err = upload_small(devid, m_head, head.data(), head.size());
+  if(err != DT_HIP_SUCCESS)
+  {
+    release();
+    return err;
+  }
+  pd_seg_t *segs = (pd_seg_t *)m_segs;
+  pstate_t *st = (pstate_t *)m_st;
+  {
+    launch_scope ls(devid, "png_filter");
+    png_filter<<<height, PT, 0, s>>>(dev_in, width, d->bit_depth, (uint8_t *)m_fs);
+  }
+  {
+    launch_scope ls(devid, "png_lz");
+    png_lz<<<(unsigned)nseg, PT, 0, s>>>((const uint8_t *)m_fs, N, level, (uint32_t *)m_m, (uint64_t *)m_tok,
+                                         (uint64_t *)m_mat, (uint32_t *)m_freq, segs);
+  }
+  {
+    launch_scope ls(devid, "png_tables");
+    png_tables<<<(unsigned)nseg, 64, 0, s>>>((const uint32_t *)m_freq, N, level, segs);
+  }
+  {
+    launch_scope ls(devid, "png_scan");
+    png_scan<<<1, PT, 0, s>>>(segs, nseg, N, (uint32_t)head.size(), d->capacity, (uint64_t *)m_off, st,
+                              (uint8_t *)dev_out);
+  }
+  {
+    launch_scope ls(devid, "png_emit");
+    png_zero<<<stream_grid(nwords, PT), PT, 0, s>>>((uint32_t *)m_words, st);
+    png_emit<<<(unsigned)nseg, PT, 0, s>>>((const uint8_t *)m_fs, (const uint32_t *)m_m, (const uint64_t *)m_tok,
+                                           (const uint64_t *)m_mat, segs, (const uint64_t *)m_off, nseg,
+                                           (uint32_t *)m_words);
+    png_tail<<<1, 64, 0, s>>>((uint32_t *)m_words, pd_zlib_header(level), st);
+  }
+  {
+    launch_scope ls(devid, "png_idat");
+    png_idat<<<(unsigned)std::min<uint64_t>(max_idat, 2048), PT, 0, s>>>((const uint8_t *)m_words, st,
+                                                                          (uint32_t)head.size(), crc_type,
+                                                                          (uint8_t *)dev_out);
+    png_head<<<1, PT, 0, s>>>((const uint8_t *)m_head, (uint32_t)head.size(), st, (uint8_t *)dev_out);
+  }
+  release();
+  return check_launch("export_png");
+}

@@ -911,6 +911,7 @@ size_t dt_hip_abi_sizeof(const char *name)
   S("tile_plan_roi", dt_hip_tile_plan_roi_t);
   S("export_rows", dt_hip_export_rows_t);
   S("jpeg", dt_hip_jpeg_data_t);
+  S("png", dt_hip_png_data_t);
   S("tile_plan", dt_hip_tile_plan_t);
   S("band", dt_hip_band_t);
   S("band_state", dt_hip_band_state_t);

@@ -244,3 +244,28 @@ def jpeg(quality, icc=None, dpi=None):
         d.icc = C.cast(d._icc, C.c_void_p)
         d.icc_bytes = len(icc)
     return d
+
+
+def png(bpp=8, compression=5, icc=None, dpi=None):
+    """dt_hip_png_data_t for an Ansel PNG export (write_image() of src/imageio/format/png.c, recalled, not checked
+    against the Ansel source: DESIGN.md section 4.7): RGB without alpha, not interlaced, `bpp` 8 (the export dialog's
+    default) or 16, png_set_compression_level(`compression`) with the dialog's 0..9 (default 5), libpng's default filter
+    choice, 16-bit samples big-endian.  icc: the output profile's bytes (iCCP), kept alive by the returned struct.
+    dpi: None (no pHYs) or dots per inch.  `capacity` is left 0: set it to the output buffer's size (dt_hip_png_bound())."""
+    b, c = int(bpp), int(compression)
+    if b not in (8, 16):
+        raise ValueError("PNG bpp %r: the device writes 8 or 16 bits" % (bpp,))
+    if not 0 <= c <= 9:
+        raise ValueError("PNG compression %r is outside 0..9" % (compression,))
+    d = abi.PngData(bit_depth=b, compression_level=c, dpi=0)
+    if dpi is not None:
+        v = int(round(dpi))
+        if v <= 0:
+            raise ValueError("dpi %r is not positive" % (dpi,))
+        d.dpi = v
+    if icc:
+        icc = bytes(icc)
+        d._icc = C.create_string_buffer(icc, len(icc))
+        d.icc = C.cast(d._icc, C.c_void_p)
+        d.icc_bytes = len(icc)
+    return d

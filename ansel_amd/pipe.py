@@ -20,6 +20,7 @@ MODULE_BPP = {
     "bilat": (16 + 16, 16),  # splat reads L, slice reads + writes the plane (48 B/px)
     "flip": (16, 16),
     "export_u8": (16, 4), "export_jpeg": (4, 0),
+    "export_png": (4, 0),  # 8 bits: node_bytes_per_px() reads 8 B/px at 16 bits
 }
 
 
@@ -66,6 +67,23 @@ def with_jpeg(nodes, jpeg_data):
 def jpeg_bound(width, height, jpeg_data):
     """dt_hip_jpeg_bound(): a capacity the encoder's output always fits"""
     return int(lib.load().dt_hip_jpeg_bound(width, height, C.byref(jpeg_data)))
+
+
+def with_png(nodes, png_data):
+    """the node list with export_png appended behind its trailing export_u16 (png_data: params.png() or an abi.PngData,
+    its capacity set -- png_bound()); at 8 bits the export_u16 is swapped for export_u8 first.  The node's output is the
+    little-endian uint64 file length, then the file.  The other nodes are shared with `nodes`."""
+    if not nodes or nodes[-1].op != "export_u16":
+        raise ValueError("with_png: the node list does not end in export_u16")
+    last = nodes[-1]
+    w, h = last.piece.roi_out.width, last.piece.roi_out.height
+    head = list(nodes) if png_data.bit_depth == 16 else list(nodes[:-1]) + [Node("export_u8", None, last.piece)]
+    return head + [Node("export_png", png_data, abi.Piece.make(w, h, channels=4))]
+
+
+def png_bound(width, height, png_data):
+    """dt_hip_png_bound(): a capacity the encoder's output always fits"""
+    return int(lib.load().dt_hip_png_bound(width, height, C.byref(png_data)))
 
 
 def light_pipe_nodes(width, height, lut_target_ptr, lut_first, lut_coeffs, with_filmic=True, filmic=None,
@@ -135,6 +153,8 @@ def node_bytes_per_px(n):
     if n.op == "diffuse":
         from . import modinfo
         return 96 * max(int(n.data.iterations), 1) * modinfo.diffuse_scales(n.piece, n.data)
+    if n.op == "export_png":
+        return int(n.data.bit_depth) // 2  # RGBA u8 or u16 in, the file (a fraction of it) out
     return sum(MODULE_BPP[n.op])
 
 

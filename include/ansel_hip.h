@@ -468,6 +468,29 @@ size_t dt_hip_jpeg_bound(int width, int height, const dt_hip_jpeg_data_t *d); /*
 int dt_hip_export_jpeg(int devid, int width, int height, const dt_hip_jpeg_data_t *d, dt_hip_mem_t dev_in_rgba8,
                        dt_hip_mem_t dev_out);
 
+/* PNG export: the file src/imageio/format/png.c write_image() makes with libpng (RGB, 8 or 16 bits, no interlace), on
+ * the device (ansel_amd/csrc/png.hip): libpng 1.6's filtered stream byte for byte, deflated in parallel segments into
+ * one valid zlib stream (not zlib's bytes).  dev_in: width x height RGBA u8 (export_u8, bit_depth 8) or RGBA u16
+ * (export_u16, bit_depth 16); alpha is ignored.  dev_out receives a little-endian uint64 file length L, then the L bytes
+ * of the file (signature, IHDR, iCCP, pHYs, IDAT chunks, IEND).  If 8 + L exceeds `capacity` the length word is
+ * UINT64_MAX and nothing is written past `capacity`; the call does not wait for the device, so the caller reads the
+ * word.  dt_hip_png_bound(): a capacity that always suffices (0 for refused settings).  Refused with
+ * DT_HIP_INVALID_ARG: width or height below 1, a bound beyond size_t, a bit depth other than 8 or 16, a compression
+ * level outside 0..9.  In a pipe: node "export_png" (data dt_hip_png_data_t), the last node, directly behind
+ * "export_u8" (8 bits) or "export_u16" (16 bits); its output is `capacity` bytes. */
+typedef struct dt_hip_png_data_t
+{
+  int32_t bit_depth;         /* 8 or 16 */
+  int32_t compression_level; /* 0..9: 0 stored blocks only, 1-3 greedy matching, 4-9 lazy */
+  int32_t dpi;               /* 0: no pHYs; else pHYs of dpi / 0.0254 pixels per metre, rounded */
+  uint64_t capacity;         /* bytes of dev_out, the 8-byte length word included */
+  const void *icc;           /* host memory, may be NULL: the iCCP profile; copied by the call (and by dt_hip_pipe_add_node) */
+  uint64_t icc_bytes;
+} dt_hip_png_data_t;
+size_t dt_hip_png_bound(int width, int height, const dt_hip_png_data_t *d); /* pure, no device */
+int dt_hip_export_png(int devid, int width, int height, const dt_hip_png_data_t *d, dt_hip_mem_t dev_in,
+                      dt_hip_mem_t dev_out);
+
 /* diffuse or sharpen: process(), src/iop/diffuse.c:1155-1258 -> wavelets_process() (:978-1106),
  * decompose_2D_Bspline() (src/pixel/bspline.h:351-377), heat_PDE_diffusion() (diffuse.c:760-968).
  * The struct is dt_iop_diffuse_params_t (diffuse.c:76-105; commit_params memcpy's it, :133-138)
