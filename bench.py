@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- MPix/s of the full-resolution export pixelpipe on MI355X, with the HBM roofline of
-the dominant kernel and the reference's CPU path timed beside it.
+the dominant kernel and (--full) the reference's CPU path timed beside it.
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -22,10 +23,15 @@ an 8-byte all-reduce and one 9-row halo send/recv per frame -> "scaling": "stron
 Started WITHOUT a launcher (`python bench.py --gpus N`, WORLD_SIZE unset) it spawns its own N ranks under
 torch.distributed.run on 127.0.0.1; a launcher whose WORLD_SIZE disagrees with --gpus is an error.
 
-Besides `value` the line carries, at N = 1: `config.light_pipe` -- config 2's module list on the SAME 100 MP
-frame, timed in the same run (and, as `config.light_pipe.with_amaze`, once more with AMaZE in RCD's place); `verified` -- the output buffer the timed steps wrote, compared word for word with
-the oracle's chain after the timed region (the oracle is the checker here, never the thing measured);
-`cpu_baseline` -- the reference's own code on the host cores, same module chain.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: `value`, `ms_per_step`, the
+per-kernel times of the timed steps (HIP events) and the roofline figures derived from them and the committed counter tables.
+Everything else runs only with --full, after the timed region.  Besides `value` the line then carries, at N = 1:
+`config.light_pipe` -- config 2's module list on the SAME 100 MP frame, timed in the same run (and, as
+`config.light_pipe.with_amaze`, once more with AMaZE in RCD's place); `config.default_diffuse`, `config.full_pipe_24MP`, the
+host-to-host legs and `roofline.peak_measured` (a copy / triad / fill / sum measured on the device); `verified` -- the output
+buffer the timed steps wrote, compared word for word with the oracle's chain after the timed region (the oracle is the checker
+here, never the thing measured); `cpu_baseline` -- the reference's own code on the host cores, same module chain.  N > 1 and
+--mode tiled / bands check their ranks' or bands' outputs with --full as well.
 
 PyTorch is used for device memory, the stream and torch.distributed only; all pixel work goes
 through the C-ABI of libansel_hip.so (include/ansel_hip.h).  There is no CPU fallback.
@@ -53,14 +59,17 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", default="100MP", help="24MP | 45MP | 60MP | 100MP | WxH")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the comparison with the oracle, "
+                         "the other pipes and frame sizes, the measured copy ceiling, the host-to-host legs and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the post-timing comparison of the timed output buffer with the oracle chain")
+                    help="--full without the post-timing comparison of the timed output buffer with the oracle chain")
     ap.add_argument("--no-light-pipe", action="store_true",
-                    help="skip the config.light_pipe leg (config 2's modules on the same frame)")
+                    help="--full without the config.light_pipe, config.default_diffuse and config.full_pipe_24MP legs")
     ap.add_argument("--light-steps", type=int, default=10, help="timed steps of the config.light_pipe leg")
     ap.add_argument("--no-host-legs", action="store_true",
-                    help="skip the PCIe-inclusive host-to-host measurements (--pipe light only; never `value`)")
+                    help="--full without the PCIe-inclusive host-to-host measurements (never `value`)")
     ap.add_argument("--no-fusion", action="store_true", help="one launch per module (A/B against the fused executor)")
     ap.add_argument("--cpu-sample", default=None,
                     help="frame size of the bounded CPU sample (default: 24MP)")
@@ -677,13 +686,14 @@ def bands_mode(args):
     elapsed = time.perf_counter() - t0
     st = abi.BandStats()
     l.dt_hip_pipe_bands_stats(C.byref(st))
+    verifying = args.full and not args.no_verify
     whole = None
-    if args.dump_outputs or not args.no_verify:
+    if args.dump_outputs or verifying:
         whole = np.concatenate([t.cpu().numpy().view(np.uint16) for t in outs], axis=0)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, whole, width, height)
     verify = None
-    if not args.no_verify:
+    if verifying:
         class _H:  # verify_output() takes a tensor-like with .cpu().numpy()
             def cpu(self):
                 return self
@@ -815,11 +825,11 @@ def main():
         dump_outputs(args.dump_outputs, out16, width, my_rows, prefix="rank%d_" % rank if world > 1 else "",
                      budget=DUMP_BYTES // world)
 
-    # ---- --mode tiled validates itself (after the timed region): every rank digests the band its timed steps wrote, rank 0
-    #      runs the SAME frame unsplit through the same executor and compares band by band -- the assembled bands are the
-    #      unsplit frame or the line says so.  What the collectives moved and how many ranks RCCL saw go on the line too.
+    # ---- with --full, --mode tiled validates itself (after the timed region): every rank digests the band its timed steps
+    #      wrote, rank 0 runs the SAME frame unsplit through the same executor and compares band by band -- the assembled bands
+    #      are the unsplit frame or the line says so.  What the collectives moved and how many ranks RCCL saw go on the line too.
     tiled_check = None
-    if args.mode == "tiled":
+    if args.mode == "tiled" and args.full:
         mine = band_digest(out16)
         if world > 1:
             digests = [None] * world
@@ -846,10 +856,10 @@ def main():
                            "exchanges_last_frame": [{k: {"calls": v[0], "bytes_sent": v[1]} for k, v in sorted(lg.items())} for lg in logs],
                            "band_rows": [int(b.rows) for b in bands]}
 
-    # ---- after the timed region: the buffer those steps wrote, against the oracle
+    # ---- with --full, after the timed region: the buffer those steps wrote, against the oracle
     verify = None
     ranks_check = None
-    if args.mode == "batch" and world > 1 and not args.no_verify:
+    if args.full and args.mode == "batch" and world > 1 and not args.no_verify:
         # N > 1, one frame per GPU: every rank also runs RANK 0's frame once and the digests must agree -- together with rank
         # 0's comparison against the oracle below that pins every device's output, not only the first one's
         same_in = torch.from_numpy(synth.bayer_mosaic_tiled(width, height, seed=1).view(np.int16)).to(dev)
@@ -864,7 +874,7 @@ def main():
         except Exception:
             rccl = None
         ranks_check = {"ranks_seen": dist.get_world_size(), "rccl_version": rccl, "all_ranks_equal_on_rank0_frame": len(set(digests)) == 1}
-    if rank == 0 and args.mode == "batch" and not args.no_verify:
+    if args.full and rank == 0 and args.mode == "batch" and not args.no_verify:
         verify = verify_output(out16, raw_host, width, height, with_filmic, args.pipe)
         if ranks_check is not None:
             verify.update(ranks_check)
@@ -872,7 +882,7 @@ def main():
 
     # ---- config 2's module list on the SAME frame, same run (config.light_pipe)
     light = None
-    if rank == 0 and world == 1 and args.mode == "batch" and args.pipe != "light" and not args.no_light_pipe:
+    if args.full and rank == 0 and world == 1 and args.mode == "batch" and args.pipe != "light" and not args.no_light_pipe:
         lnodes = build_pipe(width, height, lut.data_ptr(), lut_host, with_filmic, "light")
         lexec = pipe.DevicePipe(devid, lnodes, fusion=not args.no_fusion)
         lout = torch.empty((height, width, 4), dtype=torch.int16, device=dev)  # `out16` keeps the timed steps' frame
@@ -924,7 +934,7 @@ def main():
 
     # ---- the metric's pipe with diffuse or sharpen at the module's $DEFAULT (1 iteration, all speeds 0) instead of the timed preset
     default_diffuse = None
-    if rank == 0 and world == 1 and args.mode == "batch" and args.pipe == "full" and not args.no_light_pipe:
+    if args.full and rank == 0 and world == 1 and args.mode == "batch" and args.pipe == "full" and not args.no_light_pipe:
         dnodes = build_pipe(width, height, lut.data_ptr(), lut_host, with_filmic, "full", diffuse=DIFFUSE_DEFAULT)
         dexec = pipe.DevicePipe(devid, dnodes, fusion=not args.no_fusion)
         dout = torch.empty((height, width, 4), dtype=torch.int16, device=dev)
@@ -946,10 +956,10 @@ def main():
     #      chunks are 69 rows high -- until round 5 the grid of the half-rate second version (round 4's review, "weak" item 4: no
     #      record ran the full pipe at 24 MP); verified against the oracle like the timed frame
     full24 = None
-    if rank == 0 and world == 1 and args.mode == "batch" and args.pipe == "full" and args.size == "100MP" and not args.no_light_pipe:
+    if args.full and rank == 0 and world == 1 and args.mode == "batch" and args.pipe == "full" and args.size == "100MP" and not args.no_light_pipe:
         full24 = full_pipe_leg(torch, np, pipe, synth, l, devid, dev, "24MP", lut, lut_host, with_filmic, not args.no_fusion,
                                verify=not args.no_verify)
-    ceiling = measured_ceiling(torch, dev) if rank == 0 else None
+    ceiling = measured_ceiling(torch, dev) if args.full and rank == 0 else None
 
     # ---- the same step with the boundary's two PCIe legs (never `value`): sensor buffer in pinned host memory ->
     #      basebuffer upload -> pipe -> exported frame back into pinned host memory
@@ -959,7 +969,7 @@ def main():
     host_rows_writer_ms = None
     # (round 6: also for the metric's own workload, --pipe full -- the sequential and the overlapped leg; the two writer-side legs
     #  stay with the light pipe, where the bus and not the kernels is the bound)
-    if rank == 0 and world == 1 and args.mode == "batch" and not args.no_host_legs and args.pipe in ("light", "full"):
+    if args.full and rank == 0 and world == 1 and args.mode == "batch" and not args.no_host_legs and args.pipe in ("light", "full"):
         nb_in, nb_out = raw_host.nbytes, npix * 8
         pin_in, pin_out = l.dt_hip_alloc_host_pinned(nb_in), l.dt_hip_alloc_host_pinned(nb_out)
         if pin_in and pin_out:
@@ -1207,7 +1217,7 @@ def main():
         if verify is not None:
             line["verified"] = verify["verified"]
             line["verify"] = verify
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sample = args.cpu_sample or "24MP"
             cb = cpu_baseline_in_child(sample, with_filmic, args.pipe, (width, height))
             if cb is not None:

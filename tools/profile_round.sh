@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 Q="--no-cpu-baseline --no-host-legs --no-verify --no-light-pipe"
-python bench.py "$@" > "$OUT/bench.log" 2>&1
+python bench.py --full "$@" > "$OUT/bench.log" 2>&1
 tail -1 "$OUT/bench.log"
 # the timed region alone (the pipe bench.py's `value` is quoted on, --pipe full unless the arguments say otherwise): kernel
 # stats and the HBM byte counters bench.py's roofline.traffic / kernel_bounds cite
