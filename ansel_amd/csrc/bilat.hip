@@ -36,7 +36,7 @@ __device__ __forceinline__ int axis(const float v, const float sigma, const int 
 
 #ifdef ANSEL_HIP_MEASURING // the first gather: A/B timing only (ANSEL_HIP_BILAT_SPLAT_V1); bilat_splat2 below is the product's
 // dt_bilateral_splat(), bilateral.c:183-256, gathered per grid node
-// Row bands (a frame over several GPUs, pipe.cpp): a band splats its OWN rows [row_lo, row_hi) of the frame on top of
+// Row bands (a frame over several GPUs, pipe_bands.cpp): a band splats its OWN rows [row_lo, row_hi) of the frame on top of
 // what the bands above it have accumulated (`accumulate`: the node's z column starts from `buf` instead of zero) --
 // rows ascend from band to band, so every cell still adds its contributions in pixel row-major order, the binary32
 // partial sums travelling through `buf` unchanged.  `in` is the band's first row.  Whole frame: 0, height, 0.
@@ -541,7 +541,7 @@ int bilat_blur_and_slice(int devid, const grid_t &b, float *buf, const dt_hip_bi
 
 namespace ansel
 {
-// ---- row bands (pipe.cpp): the grid is ONE accumulation over the frame in pixel order, so the
+// ---- row bands (pipe_bands.cpp): the grid is ONE accumulation over the frame in pixel order, so the
 // bands splat one after the other into the same grid (a relay: band k starts from what bands 0..k-1 left, a few
 // hundred KB travelling from GPU to GPU), the last band's grid is broadcast, and every band blurs its copy and slices
 // its own rows.  Bit-identical to the unsplit module.

@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256) void dn_decompose(const float4 *__restrict__ i
                                                     const int in_rows)
 {
   // `height` rows are computed.  Normally they are the whole input (in_row0 = 0, in_rows = height); on a row band
-  // (pipe.cpp) the input additionally holds in_row0 halo rows above and in_rows - in_row0 - height below them
+  // (pipe_bands.cpp) the input additionally holds in_row0 halo rows above and in_rows - in_row0 - height below them
   __shared__ double runs[4][4];
   const int bx = xcd_col(); // hip_common.h: the column block, pinned to an XCD for 64 rows of the walk
   if(bx >= nseg) return;
@@ -1213,7 +1213,7 @@ int wavelets_runnable(const dt_hip_piece_t *piece, const dn_setup &s)
 namespace ansel
 {
 
-// ---- row bands (pipe.cpp) --------------------------------------------------------------
+// ---- row bands (pipe_bands.cpp) --------------------------------------------------------------
 // The band computes its OWN rows of every wavelet scale.  Scale k reads 2 * 2^k rows of scale k - 1 on either side, so
 // before each decomposition the neighbours' rows of the current coarse plane are fetched: the module input comes in
 // with 2 halo rows, and every decomposition writes its coarse plane into the middle of a buffer laid out for the next,

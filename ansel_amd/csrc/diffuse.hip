@@ -975,7 +975,7 @@ namespace ansel
 // dt_hip_test_diffuse_probe(): where the next calls report which sequence ran (tests only; nullptr: nowhere)
 static void *g_diffuse_probe = nullptr;
 
-// first_row: the frame row of the buffer's first row (a row band, pipe.cpp) -- it only enters the seeds of the
+// first_row: the frame row of the buffer's first row (a row band, pipe_bands.cpp) -- it only enters the seeds of the
 // inpainting noise, which the reference derives from the pixel's index in the frame
 static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diffuse_data_t *d, int first_row, dt_hip_mem_t dev_in,
                        dt_hip_mem_t dev_out, const dt_hip_lab_data_t *post_lab);

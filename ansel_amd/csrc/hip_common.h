@@ -147,7 +147,7 @@ struct rcd_band_t
   int out_row0, out_rows; // frame rows held by the output buffer
 };
 
-// A row band in front of a stencil module (pipe.cpp): the input buffer holds frame rows
+// A row band in front of a stencil module (pipe_bands.cpp): the input buffer holds frame rows
 // from buf_row0 on (own rows + the halo fetched from the neighbours), the band owns frame rows [row0, row1)
 struct band_view_t
 {

@@ -1344,7 +1344,7 @@ namespace ansel
 static nlm_core_params_t nlmeans_params(const dt_hip_piece_t *piece, const dt_hip_nlmeans_data_t *d);
 
 // rows/columns of input a chunk's patches touch beyond the chunk (a.reach of the launch) + the chunk height:
-// what a row band needs from its neighbours (pipe.cpp)
+// what a row band needs from its neighbours (pipe_bands.cpp)
 int nlmeans_core_halo_rows(const int frame_h, const nlm_core_params_t &p)
 {
   const int K = p.search_radius;

@@ -1,4 +1,4 @@
-// pipe_fused.h -- launchers of the fused stage groups (pipe_fused.hip), used by the executor (pipe.cpp)
+// pipe_fused.h -- launchers of the fused stage groups (pipe_fused.hip), used by the executor (pipe.cpp, pipe_bands.cpp)
 #pragma once
 #include "hip_common.h"
 

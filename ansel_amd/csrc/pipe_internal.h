@@ -1,0 +1,179 @@
+// pipe_internal.h -- what the translation units of the executor share: the module table, the node list with its plan,
+// and the handle of a device buffer (pipe.cpp, pipe_batch.cpp, pipe_bands.cpp, pipe_tiling.cpp).
+// Not part of the C-ABI (that is include/ansel_hip.h).
+#pragma once
+#include "hip_common.h"
+#include "pipe_fused.h"
+
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace ansel
+{
+
+// The index of k_ops[].  OP_EXPOSURE ... OP_COLOROUT are contiguous and in the reference's pipe order (exposure <
+// colorin < channelmixerrgb < filmicrgb < colorout, src/develop/iop_order.c): dt_hip_pipe_t::plan() tests "a stage of
+// the fused RGBA run" as a range of this enum and "the run walks the pipe order" by comparing its values
+enum op_t
+{
+  OP_RAWPREPARE,
+  OP_TEMPERATURE,
+  OP_HIGHLIGHTS,
+  OP_DEMOSAIC,
+  OP_DENOISEPROFILE,
+  OP_EXPOSURE,
+  OP_COLORIN,
+  OP_CHANNELMIXERRGB,
+  OP_FILMICRGB,
+  OP_COLOROUT,
+  OP_DIFFUSE,
+  OP_RGB_TO_LAB,
+  OP_NLMEANS,
+  OP_BILAT,
+  OP_LAB_TO_RGB,
+  OP_FINALSCALE,
+  OP_INITIALSCALE,
+  OP_EXPORT_U16,
+  OP_BLEND,
+  OP_EXPORT_ROWS,
+  OP_EXPORT_U8,
+  OP_DETAILMASK,
+  OP_FLIP, // changes the geometry (SWAP_XY): never inside a fused group
+  OP_EXPORT_JPEG, // the last node, behind export_u8: a file, not pixels
+  OP_EXPORT_PNG,  // the last node, behind export_u8 (8 bits) or export_u16 (16 bits): a file
+  OP_UNKNOWN
+};
+static_assert(OP_COLORIN == OP_EXPOSURE + 1 && OP_CHANNELMIXERRGB == OP_EXPOSURE + 2 && OP_FILMICRGB == OP_EXPOSURE + 3
+                && OP_COLOROUT == OP_EXPOSURE + 4,
+              "plan() relies on exposure ... colorout being contiguous and in the reference's pipe order");
+
+struct node_t
+{
+  op_t op;
+  dt_hip_piece_t piece;
+  std::vector<unsigned char> data;
+  std::vector<unsigned char> icc; // export_jpeg / export_png: the node's copy of the ICC profile its data pointed to
+  template <typename T> const T *as() const { return reinterpret_cast<const T *>(data.data()); }
+};
+
+enum
+{
+  OPF_CFA = 1,     // works on the mosaic: the first stage of a row band (dt_hip_pipe_band_begin())
+  OPF_STENCIL = 2, // reads rows beyond its own: a row band stops in front of it for the neighbours' rows
+  OPF_NO_PTP = 4   // dt_hip_default_process_tiling_ptp() cannot run it tile by tile
+};
+
+// One row per module: everything the executor, the band walk and the tile drivers know about it
+struct op_info_t
+{
+  op_t op; // the row's own index (checked at compile time, pipe.cpp)
+  const char *name;
+  size_t data_size;
+  int bpp_out;                         // bytes per pixel of the module output; 0: 4 bytes per channel, as the input
+  size_t (*out_size)(const node_t &n); // the export nodes whose output size comes from their data (then bpp_out is not read)
+  int (*run)(int devid, const node_t &n, dt_hip_mem_t in, dt_hip_mem_t out);
+  unsigned flags; // OPF_*
+  // rows of its input the module's own rows depend on beyond a band (-1: no row-band implementation, or the module passes
+  // this frame through); nullptr: none
+  int (*halo_rows)(const node_t &n);
+};
+extern const op_info_t k_ops[OP_UNKNOWN];
+
+// (name, piece, data) -> node, with the node's own copy of what the data points to.  DT_HIP_INVALID_ARG with the last error
+// set ("<who>: ...") for a name without a row in k_ops[] and for data of another size than the module's struct
+int make_node(node_t &n, const char *who, const char *name, const dt_hip_piece_t *piece, const void *data, size_t data_size);
+size_t out_bytes(const node_t &n);
+static inline int run_single(int devid, const node_t &n, dt_hip_mem_t in, dt_hip_mem_t out) { return k_ops[n.op].run(devid, n, in, out); }
+static inline int band_halo_rows(const node_t &n) { return k_ops[n.op].halo_rows ? k_ops[n.op].halo_rows(n) : 0; }
+
+// A device buffer of a walk: the allocation, the byte offset of the view into it that the launches read or write (a band's
+// own rows inside a [halo][rows][halo] layout), and whether the handle owns the allocation.  An owned allocation goes back to
+// the runtime's pool when the handle is released, assigned to or destroyed (stream-ordered: safe behind the launches that
+// are enqueued); a borrowed one (the caller's dev_in / dev_out) is left alone.
+class dev_buf_t
+{
+  dt_hip_mem_t base_ = nullptr;
+  size_t offset_ = 0;
+  bool owned_ = false;
+
+public:
+  dev_buf_t() = default;
+  dev_buf_t(dt_hip_mem_t base, bool owned, size_t offset = 0) : base_(base), offset_(offset), owned_(owned) {}
+  // from the pool; empty when the pool has nothing to give
+  static dev_buf_t alloc(int devid, size_t bytes, size_t offset = 0) { return dev_buf_t(dt_hip_alloc_device_buffer(devid, bytes), true, offset); }
+  static dev_buf_t borrow(dt_hip_mem_t base) { return dev_buf_t(base, false); }
+  dev_buf_t(dev_buf_t &&o) noexcept : base_(o.base_), offset_(o.offset_), owned_(o.owned_) { o.base_ = nullptr; }
+  dev_buf_t &operator=(dev_buf_t &&o) noexcept
+  {
+    if(this != &o)
+    {
+      release();
+      base_ = o.base_, offset_ = o.offset_, owned_ = o.owned_;
+      o.base_ = nullptr;
+    }
+    return *this;
+  }
+  dev_buf_t(const dev_buf_t &) = delete;
+  dev_buf_t &operator=(const dev_buf_t &) = delete;
+  ~dev_buf_t() { release(); }
+  void release()
+  {
+    if(base_ && owned_) dt_hip_release_mem_object(base_);
+    base_ = nullptr;
+  }
+  explicit operator bool() const { return base_ != nullptr; }
+  bool owned() const { return base_ && owned_; }
+  dt_hip_mem_t base() const { return base_; }
+  size_t offset() const { return offset_; }
+  dt_hip_mem_t ptr() const { return base_ ? (dt_hip_mem_t)((char *)base_ + offset_) : nullptr; }
+};
+
+struct group_t
+{
+  enum kind_t { SINGLE, RAW, RGB } kind;
+  int first, count; // node range
+  raw_group_t raw;
+  rgb_group_t rgb;
+};
+
+// what a check of the node list found: kept with the plan, reported by every call on that node list
+struct plan_error_t
+{
+  int code = DT_HIP_SUCCESS;
+  std::string text;
+  // the text just given to set_last_error()
+  int keep(const int c)
+  {
+    code = c;
+    text = dt_hip_last_error();
+    return c;
+  }
+  int report() const
+  {
+    if(code != DT_HIP_SUCCESS) set_last_error("%s", text.c_str());
+    return code;
+  }
+};
+
+} // namespace ansel
+
+struct dt_hip_pipe_t
+{
+  int devid = 0;
+  bool fusion = true;
+  bool planned = false;
+  bool dropped_flip = false; // the last node added was a flip of orientation 0 (not kept)
+  std::vector<ansel::node_t> nodes;
+  // what plan() makes of the node list
+  std::vector<ansel::group_t> groups;
+  ansel::plan_error_t placement; // a node in a place where dt_hip_pipe_process() cannot run it
+  // a node without a row-band implementation: looked for by the first dt_hip_pipe_band_begin() on this plan (pipe_bands.cpp)
+  bool band_checked = false;
+  ansel::plan_error_t band_mode;
+
+  void plan(); // pipe.cpp
+  bool is_blend_group(const size_t k) const { return k < groups.size() && nodes[groups[k].first].op == ansel::OP_BLEND; }
+  // the group's output is the pipe's: it is the last group, or only the blend of its module follows
+  bool is_final_group(const size_t k) const { return k + 1 == groups.size() || (is_blend_group(k + 1) && k + 2 == groups.size()); }
+};

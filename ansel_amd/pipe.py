@@ -163,7 +163,7 @@ def algorithmic_bytes_per_pixel(nodes):
 
 
 class DevicePipe:
-    """dt_hip_pipe_t: the C++ executor of libansel_hip (pipe.cpp) loaded with a node list"""
+    """dt_hip_pipe_t: the C++ executor of libansel_hip (csrc/pipe.cpp; batches, row bands and tiling in pipe_batch.cpp, pipe_bands.cpp, pipe_tiling.cpp) loaded with a node list"""
 
     def __init__(self, devid, nodes, fusion=True):
         self.lib = lib.load()

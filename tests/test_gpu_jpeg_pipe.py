@@ -1,4 +1,4 @@
-"""-m gpu: the "export_jpeg" node of the executor (pipe.cpp) and the batch.
+"""-m gpu: the "export_jpeg" node of the executor (pipe.cpp) and the batch (pipe_batch.cpp).
 
   * the light pipe with export_u8 + export_jpeg (pipe.with_jpeg): the file equals tests/jpeg_ref.py of the oracle
     chain's u8 frame -- 24 MP, and the 100 MP frame with orientation 6 (portrait, 8736 x 11648)

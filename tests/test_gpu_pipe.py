@@ -323,6 +323,51 @@ def test_executor_returns_every_intermediate_to_the_pool():
     p.close()
 
 
+def test_abandoned_walks_return_every_buffer_to_the_pool():
+    """two ways out of a walk that hold buffers nobody else frees, each followed by the runtime's allocation counter back
+    at its baseline: a blend that refuses its parameters (an unknown colourspace) while the input of its module is held
+    for it, and a row band given up with dt_hip_pipe_band_abort() right after dt_hip_pipe_band_begin(), before the
+    highlights journal is resolved"""
+    import torch
+    from ansel_amd import tiled
+    l = hc.hip()
+    w, h = 400, 300
+    lut = params.srgb_encode_lut()
+    d_lut = torch.from_numpy(lut).to("cuda:0")
+    nodes = pipe.denoise_pipe_nodes(w, h, d_lut.data_ptr(), float(lut[0]), params.unbounded_coeffs(lut),
+                                    filmic=filmic.default_data(), diffuse_iterations=2, with_nlmeans=True, with_bilat=True)
+    raw = torch.from_numpy(synth.bayer_mosaic(w, h, seed=2).view(np.int16)).to("cuda:0")
+    res = torch.zeros((h, w, 4), dtype=torch.int16, device="cuda:0")
+    cur, peak = C.c_size_t(0), C.c_size_t(0)
+
+    def allocated():
+        torch.cuda.synchronize()
+        l.dt_hip_memory_statistics(0, C.byref(cur), C.byref(peak))
+        return cur.value
+
+    base = allocated()
+    bad = []
+    for n in nodes:
+        bad.append(n)
+        if n.op == "exposure":
+            bad.append(pipe.Node("blend", abi.BlendData.uniform(params.WORK_IN, 60.0, abi.BLEND_MULTIPLY, 0.5, blend_cst=99), n.piece))
+    p = pipe.DevicePipe(0, bad)
+    with pytest.raises(lib.AnselHipError, match="unknown colourspace"):
+        p.process(raw.data_ptr(), res.data_ptr())
+    assert allocated() == base
+    p.close()
+
+    p = pipe.DevicePipe(0, nodes)
+    band = tiled.plan_bands(w, h, 2, tiled.pipe_demosaic_method(nodes))[0]
+    st = abi.BandState()
+    assert l.dt_hip_pipe_band_begin(p.handle, C.byref(band), raw.data_ptr(), C.byref(st)) == 0
+    assert st.clipped_count and st.halo_buf    # the journal and the CFA rows in their halo layout
+    assert allocated() > base
+    l.dt_hip_pipe_band_abort(p.handle, C.byref(st))
+    assert allocated() == base
+    p.close()
+
+
 def test_lab_glue_is_fused_into_the_pointwise_runs():
     """"lab_to_rgb" in front of a fusable run and "rgb_to_lab" behind one are stages of that run's kernel: one launch, the
     same bits as the module-by-module chain"""

@@ -1,4 +1,4 @@
-"""-m gpu: the "export_png" node of the executor (pipe.cpp) and the batch.
+"""-m gpu: the "export_png" node of the executor (pipe.cpp) and the batch (pipe_batch.cpp).
 
   * the light pipe + export_png (pipe.with_png): the file decodes to exactly the oracle chain's u8 / u16 frame, alpha
     dropped -- 24 MP at 8 and 16 bits, and the 100 MP frame with orientation 6 at 8 bits; at 24 MP it equals the host
