@@ -21,8 +21,10 @@ int raw_group_launch(int devid, const raw_group_t &g, dt_hip_mem_t dev_in, dt_hi
                      dt_hip_mem_t deferred_journal = nullptr);
 bool raw_group_supported(const raw_group_t &g);
 
-// ---- fused RGBA group: any order of exposure, colorin, channelmixerrgb, filmicrgb, colorout,
-//      optionally opened / closed by the Lab glue of the pipe and closed by the float -> u16 conversion ------------------------------------------
+// ---- fused RGBA group: a run of exposure, colorin, channelmixerrgb, filmicrgb, colorout in the reference's pipe order
+//      (each at most once, any of them absent: dt_hip_pipe_t::plan() ends a run at a node that does not come later in that
+//      order than the one in front of it -- the kernel applies its stages in that order, whatever ops[] says), optionally
+//      opened / closed by the Lab glue of the pipe and closed by the float -> u16 conversion -------------------------------
 enum rgb_op_t { RGB_OP_EXPOSURE = 0, RGB_OP_COLORIN, RGB_OP_CHANNELMIXER, RGB_OP_FILMIC, RGB_OP_COLOROUT, RGB_OP_END };
 struct rgb_group_t
 {
