@@ -1065,6 +1065,10 @@ int slice_width(const int width)
 namespace ansel
 {
 
+// dt_hip_test_nlm_last(): what the last nlmeans_core_launch() that reached its launch took (tests only; host words, no GPU work)
+enum { NLM_BODY_NONE = 0, NLM_BODY_TALL, NLM_BODY_V4, NLM_BODY_V3, NLM_BODY_V2, NLM_BODY_PIPELINED, NLM_BODY_STAGED, NLM_BODY_GLOBAL };
+static int g_nlm_last[8];
+
 int nlmeans_core_launch(int devid, const float4 *in, float4 *out, int width, int height, const nlm_core_params_t &p)
 {
   if(p.band && (p.band->frame_h <= 0 || p.band->row0 < 0 || p.band->row1 > p.band->frame_h || p.band->row0 >= p.band->row1))
@@ -1280,6 +1284,18 @@ int nlmeans_core_launch(int devid, const float4 *in, float4 *out, int width, int
     return DT_HIP_DEFAULT_ERROR;
   }
   {
+    const bool third = v3 && v3_bytes <= 160 * 1024;
+    g_nlm_last[0] = tall ? NLM_BODY_TALL : v4 ? NLM_BODY_V4 : third ? NLM_BODY_V3 : v2 ? NLM_BODY_V2
+                    : pipelined ? NLM_BODY_PIPELINED : staged ? NLM_BODY_STAGED : NLM_BODY_GLOBAL;
+    g_nlm_last[1] = tight;
+    g_nlm_last[2] = deep;
+    g_nlm_last[3] = a.radius;
+    g_nlm_last[4] = a.npatch;
+    g_nlm_last[5] = a.reach;
+    g_nlm_last[6] = n_border;
+    g_nlm_last[7] = nchunks;
+  }
+  {
     launch_scope ls(devid, "nlm_chunks");
     const unsigned grid = (unsigned)nchunks;
     if(tall)
@@ -1314,6 +1330,15 @@ int nlmeans_core_launch(int devid, const float4 *in, float4 *out, int width, int
 } // namespace ansel
 
 extern "C" {
+
+// tests only (not in include/ansel_hip.h): the last launch's body (1 tall, 2 v4, 3 v3, 4 v2, 5 pipelined, 6 staged, 7 global;
+// 0: none yet), tight, deep (the second version's layout and schedule, as computed), patch radius, offsets, reach, border chunks, chunks
+int dt_hip_test_nlm_last(int out[8])
+{
+  if(!out) return DT_HIP_INVALID_ARG;
+  memcpy(out, ansel::g_nlm_last, sizeof(ansel::g_nlm_last));
+  return DT_HIP_SUCCESS;
+}
 
 int dt_hip_iop_nlmeans_process(int devid, const dt_hip_piece_t *piece, const dt_hip_nlmeans_data_t *d,
                                dt_hip_mem_t dev_in, dt_hip_mem_t dev_out)

@@ -180,6 +180,7 @@ def load():
         "dt_hip_iop_highlights_process_deferred": (i, [i, P(abi.Piece), P(abi.HighlightsData), vp, vp, vp]),
         "dt_hip_iop_highlights_resolve": (i, [i, vp, vp]),
         "dt_hip_test_dispatch": (i, [C.c_char_p, i]),
+        "dt_hip_test_nlm_last": (i, [P(i)]),
     }
     missing = []
     for name, (res, args) in protos.items():
@@ -200,6 +201,19 @@ def test_dispatch(key, value):
     """dt_hip_test_dispatch() (csrc/testhooks.hip): send launches to a fallback kernel the library carries anyway -- "nlm_v2",
     "nlm_fused", "amaze_unfused", "amaze_slab", "amaze_blocks" -- on frames where the primary kernel applies; 0 clears"""
     check(load().dt_hip_test_dispatch(key.encode(), int(value)), "dt_hip_test_dispatch(%s)" % key)
+
+
+NLM_BODIES = ("none", "tall", "v4", "v3", "v2", "pipelined", "staged", "global")
+
+
+def test_nlm_last():
+    """dt_hip_test_nlm_last() (csrc/nlmeans.hip): which body the last non-local-means launch took and its figures"""
+    out = (C.c_int * 8)()
+    check(load().dt_hip_test_nlm_last(out), "dt_hip_test_nlm_last")
+    keys = ("body", "tight", "deep", "radius", "npatch", "reach", "n_border", "nchunks")
+    d = dict(zip(keys, list(out)))
+    d["body"] = NLM_BODIES[d["body"]]
+    return d
 
 
 def check(rc, what=""):

@@ -12,9 +12,19 @@ MODULES = ["rawprepare", "temperature", "highlights", "demosaic_rcd", "demosaic_
 _KEEP = []
 
 
-def case(module, w, h, lut_ptr=None):
+# the stencil modules whose code reads roi_in.scale (the chunk offsets, the band count, the PDE's zoom, the grid's sigma)
+SCALE_READERS = ["denoiseprofile", "denoiseprofile_nlm", "nlmeans", "bilat", "diffuse"]
+
+
+def case(module, w, h, lut_ptr=None, scale=1.0):
     """-> (op, piece, data, input, output shape, pre-filled output or None); lut_ptr: where the tone curve of
-    colorout lives for the callee (a device pointer for the HIP path; default: host memory)"""
+    colorout lives for the callee (a device pointer for the HIP path; default: host memory); scale: the scale of both
+    regions of a module of SCALE_READERS (an export below or above full size)"""
+    if scale != 1.0:
+        assert module in SCALE_READERS, module
+        op, piece, data, inp, shape, pre = case(module, w, h, lut_ptr)
+        piece.roi_in.scale = piece.roi_out.scale = float(scale)
+        return op, piece, data, inp, shape, pre
     rng = np.random.default_rng(1000 * w + h)
     rgba = (rng.random((h, w, 4), dtype=np.float32) * 1.2 - 0.05).astype(np.float32)
     lab = (rgba * np.float32([100, 60, 60, 1]) - np.float32([0, 30, 30, 0])).astype(np.float32)
@@ -74,9 +84,9 @@ def case(module, w, h, lut_ptr=None):
     raise KeyError(module)
 
 
-def undefined_in_reference(module, w, h):
+def undefined_in_reference(module, w, h, scale=1.0):
     """sizes on which the reference itself reads or writes outside its buffers (it crashes on the CPU): the oracle
-    and the device refuse them"""
+    and the device refuse them; scale: the regions' scale of case(.., scale=)"""
     if module == "bilat_ll":
         # a side of 2 indexes the pyramid array at -1 (locallaplacian.c:405), a side of 3 pads for two levels
         # but builds one: out-of-bounds reads either way.  A side of 1 returns before touching anything (:366)
@@ -90,11 +100,20 @@ def undefined_in_reference(module, w, h):
         if not supp0 > 1.0:
             return False  # log2 of a non-positive number: NaN, every comparison false, 7 bands, copy-through
         i0 = np.log2((supp0 - 1.0) * 0.5)
-        return 1.0 - (np.log2((5.0 - 1.0) * 0.5) - 1.0 + 0.5) / i0 < 0.0
+        in_scale = min(scale, 1.0)  # a band's support in input pixels, denoiseprofile.c:1306-1311
+        bands = 0
+        while bands < 7 and not 1.0 - (np.log2(((2 * (2 << bands) + 1) / in_scale - 1.0) * 0.5) - 1.0 + 0.5) / i0 < 0.0:
+            bands += 1
+        if bands == 0:
+            return True
+        # fewer than 4x the coarsest dilation in a row that is not copied through (:1325-1329): eaw.c:308-323 reads before
+        # the row's start.  No size of SIZES gets there at scale 1; 2 x 64 does at 0.5, where one band is left
+        mult = 1 << (bands - 1)
+        return not (w < 2 * mult or h < 2 * mult) and w < 4 * mult
     if module == "bilat":
         import ctypes as C
         # a grid line shorter than the four entries blur_line() touches unconditionally
-        sigma_s = max(12.0, 0.5)
+        sigma_s = max(12.0 * scale, 0.5)  # sigma_s / (iscale / roi_in.scale), bilat.c:339
         _x = min(max(int(round(w / sigma_s)), 4), 6000)
         _y = min(max(int(round(h / sigma_s)), 4), 6000)
         s = max(w / _x, h / _y)

@@ -7,6 +7,8 @@
   * device_pipe / device_bands / device_bands_c / device_batch   the executor's walks over the list
   * the parameter pools of the module tests (filmic per fused mode, the five adaptations, the conversion flavours, ...)
   * generate(seed)                    a valid node list from a small grammar, its input frame and its tags
+  * generate_scaled(seed)             the same for lists whose RGBA part runs at a region scale != 1: a reduced-size export
+                                      (mosaic, demosaic, initialscale, modules at its scale) or an RGBA frame at a scale
   * plan_groups / fused_pairs / band_eligible   plain restatements of dt_hip_pipe_t::plan(), of the frame walk's fused
                                       pairs and of the band walk's refusals, over the node list alone
 
@@ -180,13 +182,13 @@ def file_of(buf):
     return np.ascontiguousarray(buf[8:8 + n]).tobytes()
 
 
-def oracle_chain(nodes, src, which="oracle", tap=None):
+def oracle_chain(nodes, src, which="oracle", tap=None, fill=0.0):
     """The unsplit CPU chain of a node list: what band_engine.whole_frame() and test_gpu_pipe._run_cpu() do for the
     canonical pipes, for any list.  which="ref": the reference's own code wherever oracle/_ref has the function, the
     oracle's elsewhere (flip, the export nodes and the encoders have no _ref function).  Returns what the last node writes;
     behind an encoder that is the file's bytes.  tap(k, node, input, output, before) sees every node's buffers: a blend's
     input is the input of its module, and `before` is a copy of that module's output as the blend found it (None at every
-    other node)."""
+    other node).  fill: what every module's output holds before the module runs -- the words a module leaves alone keep it."""
     o = ck.oracle()
     assert o is not None, "oracle/liboracle.so missing: run build()"
     r = ck.ref() if which == "ref" else None
@@ -231,7 +233,7 @@ def oracle_chain(nodes, src, which="oracle", tap=None):
         else:
             shape, dtype = _node_out(n)
             out = ck.aligned_empty(shape, dtype)
-            out[...] = 0
+            out[...] = fill
             l, name = fn(n.op)
             assert ck.call(l, name, n.piece, n.data, cur, out) == 0, "%s (node %d) refused by the checker" % (n.op, k)
             prev, cur = cur, out
@@ -445,12 +447,17 @@ def _geometry(n):
     return (n.piece.roi_out.width, n.piece.roi_out.height)
 
 
+def _roundf(v):
+    """roundf(): halves away from zero (Python's round() takes them to the even neighbour)"""
+    return int(np.copysign(np.floor(abs(v) + 0.5), v))
+
+
 def _raw_group_supported(trio):
     p = trio[0].piece
     if not (p.filters and p.filters != 9 and p.channels == 1):
         return False
     w, d = p.roi_out.width, trio[0].data
-    if w <= 0 or w % 4 or p.roi_in.width % 4 or int(round(d.x * p.roi_in.scale)) % 4:
+    if w <= 0 or w % 4 or p.roi_in.width % 4 or _roundf(float(np.float32(d.x * p.roi_in.scale))) % 4:
         return False
     for n in trio[1:]:
         if not n.piece.filters or n.piece.filters == 9 or _geometry(n) != _geometry(trio[0]):
@@ -595,9 +602,11 @@ def band_rows(width, height, method, n_bands):
 
 
 def stencil_halo_bound(n):
-    """rows of either neighbour a stencil module of the pools reads at most, on the frames of this file (the exact count
-    is dt_hip_band_halo_rows(); tests/test_pipe_cases.py holds it against this bound): the wavelets' and the non-local
-    means' below 80, diffuse-or-sharpen below 93 an iteration.  The bound makes band_eligible() conservative, never
+    """rows of either neighbour a stencil module of the pools reads at most AT REGION SCALE 1, on the frames of this file
+    (the exact count is dt_hip_band_halo_rows(); tests/test_pipe_cases.py holds it against this bound): the wavelets' and
+    the non-local means' below 80, diffuse-or-sharpen below 93 an iteration.  At another scale the patch offsets, the
+    search radius and the PDE's zoom move these figures (non-local means at scale 2 reads 96 rows and more): the scaled
+    lists of generate_scaled() take the exact count, exact_halo().  The bound makes band_eligible() conservative, never
     wrong: a list it keeps off the bands (diffuse with two iterations on three bands of these frames, say) only loses that
     walk, and one it admits is checked against the exact halo on the CPU."""
     if n.op == "diffuse":
@@ -607,10 +616,20 @@ def stencil_halo_bound(n):
     return 4 if n.op == "denoiseprofile" else 0
 
 
-def band_eligible(nodes, n_bands):
+def exact_halo(n):
+    """dt_hip_band_halo_rows() itself (a host function of the library: no GPU): the rows a node takes from either neighbour
+    at its own region scale; a module that only copies its frame through (the wavelets on a frame too small) takes none"""
+    if n.data is None or n.op == "blend":
+        return 0
+    return max(int(lib.load().dt_hip_band_halo_rows(n.op.encode(), C.byref(n.piece), C.cast(C.byref(n.data), C.c_void_p), C.sizeof(n.data))), 0)
+
+
+def band_eligible(nodes, n_bands, halo_of=None):
     """the rules check_band_mode() and dt_hip_plan_bands() state (pipe_bands.cpp), over the node list alone -- and the one
     both band drivers state when they meet it ("a band owns fewer rows than the halo its neighbour needs: use fewer
-    bands"): the halo rows of a stencil module come out of the neighbour's own rows"""
+    bands"): the halo rows of a stencil module come out of the neighbour's own rows.  halo_of: stencil_halo_bound (the
+    lists at scale 1) or exact_halo (the scaled ones)"""
+    halo_of = halo_of if halo_of is not None else stencil_halo_bound
     nodes = kept(nodes)
     w, h = _geometry(nodes[0])
     method = -1
@@ -621,7 +640,7 @@ def band_eligible(nodes, n_bands):
         return False
     rows = band_rows(w, h, method, n_bands)
     for n in nodes:
-        halo = stencil_halo_bound(n)
+        halo = halo_of(n)
         for k, (r0, nr) in enumerate(rows):
             if (k and min(halo, r0) > rows[k - 1][1]) or (k + 1 < n_bands and min(halo, h - r0 - nr) > rows[k + 1][1]):
                 return False
@@ -640,6 +659,33 @@ def band_eligible(nodes, n_bands):
             if d.feathering_radius > 0.1 or d.blur_radius > 0.0:
                 return False
     return True
+
+
+# ---- the figures of a non-local-means launch at a region scale, restated ------------------------------------------------------
+def _scatter(scale, scattering, i1, i2):
+    """scatter(), nlmeans_core.c:95-105: the scale a float, the rest binary64"""
+    a1, a2 = abs(i1), abs(i2)
+    return int(float(np.float32(scale)) * ((a1 * a1 * a1 + 7.0 * a1 * np.sqrt(a2)) * ((i1 > 0) - (i1 < 0)) * scattering / 6.0 + i1))
+
+
+def nlmeans_figures(radius, scale):
+    """denoise (non-local means), process_cpu() nlmeans.c:416-457: (patch radius P, offsets, reach = P + 1 + the largest shift)"""
+    s = np.float32(min(scale, 2.0))
+    P, K = int(np.ceil(np.float32(radius) * s)), int(np.ceil(np.float32(7.0) * s))
+    return P, (2 * K + 1) ** 2, P + 1 + _scatter(s, 0.0, K, 0)
+
+
+def dn_nlmeans_figures(d, scale):
+    """denoise (profiled), non-local-means mode, denoiseprofile.c:1599-1648 and :1476-1500: (P, K, reach, the scattering derived
+    from the scale -- it keeps the reach the user's values had at scale 1)"""
+    s = np.float32(min(min(scale, 2.0), 1.0))
+    K = int(d.nbhood)
+    P = int(np.ceil(np.float32(d.radius) * s))
+    maxk = int((K * K * K + 7.0 * K * np.sqrt(K)) * float(d.scattering) / 6.0 + K)
+    K = int(max(np.float32(min(K, 4)), np.float32(K) * s))
+    scattering = float(np.float32((maxk - K) * 6.0 / (K * K * K + 7.0 * K * np.sqrt(K))))
+    shift = max(abs(_scatter(s, scattering, i, j)) for i in range(-K, K + 1) for j in range(-K, K + 1))
+    return P, K, P + 1 + shift, scattering
 
 
 # ---- the generator ------------------------------------------------------------------------------------------------------
@@ -662,6 +708,7 @@ class _Builder:
         self.plane = None  # the raw detail mask's plane, while the frame keeps the geometry it was written in
         self.stencils = 0
         self.plain = False  # leave out what has no row-band implementation
+        self.scale = 1.0  # the scale of both regions of every piece made from here on (generate_scaled())
 
     def pick(self, seq):
         return seq[int(self.rng.integers(0, len(seq)))]
@@ -670,7 +717,10 @@ class _Builder:
         return bool(self.rng.random() < p)
 
     def rgb(self):
-        return abi.Piece.make(self.w, self.h, channels=4, processed_maximum=self.pm)
+        if self.scale == 1.0:
+            return abi.Piece.make(self.w, self.h, channels=4, processed_maximum=self.pm)
+        return abi.Piece.make(self.w, self.h, channels=4, processed_maximum=self.pm, roi_in=abi.Roi.make(0, 0, self.w, self.h, self.scale),
+                              roi_out=abi.Roi.make(0, 0, self.w, self.h, self.scale))
 
     def add(self, op, data, piece=None):
         self.nodes.append(pipe.Node(op, data, piece if piece is not None else self.rgb()))
@@ -834,6 +884,117 @@ def generate(seed, tables=None):
     return b.nodes, np.ascontiguousarray(src), tags
 
 
+# ---- lists at a region scale != 1 ----------------------------------------------------------------------------------------
+EXPORT_SCALES = (0.37, 0.5, 0.81)  # a reduced-size export: initialscale behind the demosaic, the RGBA modules at its scale
+RGBA_SCALES = (0.5, 2.0)           # an RGBA frame whose regions carry the scale: no resampler, the list stays band-eligible
+SCALED_STENCILS = ("nlmeans", "diffuse", "denoiseprofile", "bilat")
+SCALED_SEEDS = tuple(range(1, 25))
+# The demosaic leaves the fourth channel to its caller, as the reference does: RCD on its border ring, AMaZE on the whole frame
+# (rcd.c:96-127, amaze.cc); the local laplacian leaves it alone too.  The resampler, the Lab conversions, exposure,
+# channelmixerrgb, filmic v4, diffuse and the bilateral grid carry or filter what they find there, and non-local means gives NaN
+# for NaN.  These write a value of their own whatever they find:
+SETS_ALPHA = ("colorin", "colorout", "denoiseprofile")
+
+
+def alpha_is_written(nodes):
+    """the last words of the list are a function of its input: behind the last module that leaves the fourth channel of its
+    output unwritten comes one that writes it, or an ending that drops it.  Otherwise they are whatever the buffers held, on
+    the host and on the device (tests/test_pipe_cases.py holds the scaled lists to this with the oracle's buffers full of NaN)"""
+    written = True
+    for n in nodes:
+        if n.op == "demosaic" or (n.op == "bilat" and n.data.mode != 0):
+            written = False
+        elif n.op in SETS_ALPHA or (n.op == "export_rows" and n.data.layers == 3):
+            written = True
+    return written
+
+
+def generate_scaled(seed, tables=None):
+    """(nodes, src, tags) of one pipe whose RGBA part runs at a region scale != 1, in one of two shapes:
+
+        export := [rawprepare] [temperature] [highlights] demosaic initialscale(s) item+ end       s of EXPORT_SCALES
+        rgba   := item+ end        on an RGBA frame, every piece at scale s                         s of RGBA_SCALES
+        item   := pointwise modules in pipe order | denoiseprofile | diffuse | rgb_to_lab (nlmeans | bilat)+ lab_to_rgb
+        end    := float | export_u16 [export_rows] | export_u8
+
+    (a list whose draw leaves the fourth channel unwritten gets a colorout behind its items: alpha_is_written()).
+    The shape, the scale and the first stencil module go round with the seed, so that a short seed list holds every scale,
+    both shapes and every stencil module at a scale; the rest is drawn.  generate() is not touched by any of this.
+    tags: "bands" (by band_eligible() over the exact halos, exact_halo()), "batch", "shape", "scale", "start", "end", "tables"."""
+    tb = tables if tables is not None else Tables(False)
+    rng = np.random.default_rng(7000 + seed)
+    shape = ("export", "rgba")[seed % 2]
+    first = SCALED_STENCILS[(seed // 2) % len(SCALED_STENCILS)]
+    if shape == "export":
+        scale = EXPORT_SCALES[(seed // 2) % len(EXPORT_SCALES)]
+        w, h = RAW_FRAMES[int(rng.integers(0, len(RAW_FRAMES)))]
+    else:
+        scale = RGBA_SCALES[(seed // 8) % len(RGBA_SCALES)]
+        w, h = RGBA_FRAMES[int(rng.integers(0, 3))]  # (the fourth is lower than three bands' halos)
+    b = _Builder(rng, tb, w, h)
+    b.plain = shape == "rgba"
+    if shape == "export":
+        mosaic = synth.bayer_mosaic(w, h, seed=100 + seed)
+        u16 = b.chance(0.5)
+        rng_f = float(synth.WHITE - synth.BLACK)
+        src = mosaic if u16 else mosaic.astype(np.float32)
+        b.add("rawprepare", abi.RawprepareData(0, 0, 0, 0, abi.f4(*[synth.BLACK] * 4), abi.f4(*[rng_f] * 4)),
+              abi.Piece.make(w, h, filters=synth.FILTERS_RGGB, channels=1, datatype=abi.DT_HIP_TYPE_UINT16 if u16 else abi.DT_HIP_TYPE_FLOAT))
+        if b.chance(0.7):
+            b.add("temperature", abi.TemperatureData(abi.f4(*synth.WB_COEFFS)),
+                  abi.Piece.make(w, h, filters=synth.FILTERS_RGGB, channels=1, processed_maximum=b.pm))
+            b.pm = synth.WB_COEFFS
+        cfa = abi.Piece.make(w, h, filters=synth.FILTERS_RGGB, channels=1, processed_maximum=b.pm)
+        if b.chance(0.5):
+            b.add("highlights", abi.HighlightsData(abi.DT_HIP_HIGHLIGHTS_CLIP, 1.0), cfa)
+        b.add("demosaic", abi.DemosaicData(0, 0, DEMOSAICS[int(rng.integers(0, len(DEMOSAICS)))], 0.0), cfa)
+        ow, oh = max(int(round(w * scale)), 1), max(int(round(h * scale)), 1)
+        b.add("initialscale", abi.FinalscaleData(int(rng.integers(0, 3))),
+              abi.Piece.make(ow, oh, processed_maximum=b.pm, roi_in=abi.Roi.make(0, 0, w, h, 1.0), roi_out=abi.Roi.make(0, 0, ow, oh, scale)))
+        b.w, b.h = ow, oh
+        start = "raw_u16" if u16 else "raw_f32"
+    else:
+        src = synth.rgba_image(w, h, seed=100 + seed, lo=-0.05, hi=1.6)
+        start = "rgba_scene"
+    b.scale = scale
+
+    def item(kind):
+        if kind in ("nlmeans", "bilat", "lab"):
+            b.add("rgb_to_lab", lab_data("rgb_to_lab", tb))
+            ops = (kind,) if kind != "lab" else b.pick((("nlmeans", "bilat"), ("bilat", "nlmeans"), ("bilat",), ("nlmeans",)))
+            if kind == "nlmeans" and b.chance(0.5):
+                ops = ("nlmeans", "bilat")
+            for op in ops:
+                b.module(op, lab=True)
+            b.add("lab_to_rgb", lab_data("lab_to_rgb", tb))
+        elif kind in ("denoiseprofile", "diffuse"):
+            b.module(kind)
+        else:
+            for op in [op for op in RUN_OPS if b.chance(0.6)] or ["exposure"]:
+                b.module(op)
+
+    if b.chance(0.5):
+        item("ordered")
+    item(first)
+    for _ in range(int(rng.integers(0, 3))):
+        kind = b.pick(("ordered", "ordered", "denoiseprofile", "diffuse", "lab"))
+        item(kind if kind == "ordered" or b.stencils < 3 else "ordered")
+    if not alpha_is_written(b.nodes):
+        # the draw left the fourth channel to the demosaic (or the local laplacian), which does not write it: the output profile
+        # closes the list, as in the product's pipe
+        b.module("colorout")
+    end = ENDINGS[int(rng.integers(0, FRAME_ENDINGS))]
+    if end in ("u16", "u16_rows"):
+        b.add("export_u16", None)
+    elif end != "float":
+        b.add("export_u8", None)
+    if end == "u16_rows":
+        b.add("export_rows", abi.ExportRowsData(16, 3))
+    bands = band_eligible(b.nodes, 2, exact_halo) and band_eligible(b.nodes, 3, exact_halo)
+    tags = {"bands": bands, "batch": True, "shape": shape, "scale": scale, "start": start, "end": end, "tables": tb}
+    return b.nodes, np.ascontiguousarray(src), tags
+
+
 def describe(nodes):
     return " ".join(n.op for n in nodes)
 
@@ -859,11 +1020,13 @@ def variant_lab_frame():
 
 
 def run_nodes_of(tb, cm=None, fm=None, present=("exposure", "colorin", "colorout"), end="u16", pre_lab=False,
-                 post_lab=False, cm_clip=True, filmic_export=True, flavour="matrix", size=VARIANT_FRAME):
+                 post_lab=False, cm_clip=True, filmic_export=True, flavour="matrix", size=VARIANT_FRAME, scale=1.0):
     """one fusable run: [lab_to_rgb] exposure colorin [channelmixerrgb] [filmicrgb] colorout [rgb_to_lab | export_u16
     [export_rows]], each of exposure / colorin / colorout only if named in `present`"""
     w, h = size
     rgb = abi.Piece.make(w, h, channels=4, processed_maximum=synth.WB_COEFFS)
+    if scale != 1.0:
+        rgb.roi_in.scale = rgb.roi_out.scale = float(scale)
     nodes = []
     if pre_lab:
         nodes.append(pipe.Node("lab_to_rgb", lab_data("lab_to_rgb", tb), rgb))
@@ -925,14 +1088,19 @@ def pairwise_kwargs(case):
     return kw
 
 
-def fused_pair_cases(tb):
+SCALED_PAIRS = ("wavelets+run-cm_none", "bilateral+run", "diffuse+rgb_to_lab", "nlmeans>bilat>run")  # one case per fused pair
+
+
+def fused_pair_cases(tb, scale=1.0):
     """(name, nodes, input kind, the pairs that fuse by rule, launch groups) for the four fused pairs of the frame walk and their
-    fallbacks.  Frames of 200 x 333: the stencil modules' oracles stay cheap."""
+    fallbacks.  Frames of 200 x 333: the stencil modules' oracles stay cheap.  scale: the scale of every piece's regions."""
     w, h = 200, 333
     rgb = abi.Piece.make(w, h, channels=4, processed_maximum=synth.WB_COEFFS)
+    if scale != 1.0:
+        rgb.roi_in.scale = rgb.roi_out.scale = float(scale)
 
     def run(fm=None, end="float", **kw):
-        return run_nodes_of(tb, cm=abi.DT_HIP_ADAPTATION_CAT16, fm=fm, end=end, size=(w, h), **kw)
+        return run_nodes_of(tb, cm=abi.DT_HIP_ADAPTATION_CAT16, fm=fm, end=end, size=(w, h), scale=scale, **kw)
 
     def N(op, data):
         return pipe.Node(op, data, rgb)
@@ -945,7 +1113,7 @@ def fused_pair_cases(tb):
     nl = abi.NlmeansData(2.0, 50.0, 0.5, 1.0)
     # dn_finish_chain<CM> (denoiseprofile.hip) is six more compiled copies of px_channelmixerrgb: one case per kind
     out = [("wavelets+run-" + ("cm_none" if cm is None else "cm_%d" % cm),
-            [N("denoiseprofile", wav)] + run_nodes_of(tb, cm=cm, end="float", size=(w, h)), "rgb", {"denoiseprofile+run"})
+            [N("denoiseprofile", wav)] + run_nodes_of(tb, cm=cm, end="float", size=(w, h), scale=scale), "rgb", {"denoiseprofile+run"})
            for cm in CM_KINDS]
     out += [
         ("wavelets+run_with_filmic", [N("denoiseprofile", wav)] + run(fm="agx_medium", end="u16"), "rgb", set()),

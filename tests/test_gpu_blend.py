@@ -332,3 +332,41 @@ def test_blend_details_threshold_full_frame():
     assert ck.call(ck.oracle(), "oracle_develop_blend", piece, d, a, want) == 0
     assert int((ck.ulp_diff(got, want) > 0).sum()) == 0
     drm.release()
+
+
+# ---- the mask's post operations at a ROI scale != 1 (blend.c:603-623, :869-881: sigma = blur_radius * roi_out.scale, the guided
+#      filter's window (int)(2 * feathering_radius * roi_out.scale + .5), at least 1) -----------------------------------------
+SCALED_MASK_CASES = BLUR_CASES + FEATHER_CASES
+
+
+def _at_scale(w, h, kind, s_in, s_out=None):
+    return abi.Piece.make(w, h, channels=1 if kind == "raw" else 4, roi_in=abi.Roi.make(0, 0, w, h, s_in),
+                          roi_out=abi.Roi.make(0, 0, w, h, s_in if s_out is None else s_out))
+
+
+@pytest.mark.parametrize("scale", [0.5, 1.5])
+@pytest.mark.parametrize("name,d,kind", SCALED_MASK_CASES, ids=[c[0] for c in SCALED_MASK_CASES])
+def test_blend_mask_blur_and_feathering_at_a_roi_scale(name, d, kind, scale):
+    """an export below or above full size: the blur's sigma and the guided filter's window follow roi_out.scale; device ==
+    oracle (== reference), and the result is not the scale-1 one wherever the mask has a post operation to scale"""
+    w, h = 131, 67
+    a, b = blend_cases.images_for(kind, w, h, 81 if name.startswith("blur") else 83)
+    got = _check(_at_scale(w, h, kind, scale), d, a, b, "%s at %g" % (name, scale))
+    one = b.copy()
+    assert ck.call(ck.oracle(), "oracle_develop_blend", abi.Piece.make(w, h, channels=1 if kind == "raw" else 4), d, a, one) == 0
+    same = np.array_equal(got.view(np.uint32), one.view(np.uint32))
+    # "-ignored": a uniform mask, or a one-channel buffer's feathering -- no post operation runs, the scale changes nothing
+    assert same == name.endswith("-ignored"), name
+    if name == "feather-display-w1":
+        # radius 0.3: (int)(0.6 s + .5) is 0 at 0.5 -- blend.c:611 raises it to the window 1 of scale 1 -- and 1 at 1.5
+        assert max(int(2 * d.feathering_radius * scale + 0.5), 1) == 1
+
+
+def test_blend_is_skipped_when_the_two_rois_differ_in_scale():
+    """blend.c:697-702: roi_in.scale != roi_out.scale leaves the module's output as it is (and says so on the reference's
+    console): the device must not touch `out` either"""
+    w, h = 131, 67
+    a, b = blend_cases.images_for("scene", w, h, 81)
+    d = dict((n, x) for n, x, _ in BLUR_CASES)["blur-scene-3"]
+    got = _check(_at_scale(w, h, "scene", 1.0, 0.5), d, a, b, "roi_in.scale != roi_out.scale")
+    assert np.array_equal(got.view(np.uint32), b.view(np.uint32))

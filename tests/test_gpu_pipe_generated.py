@@ -10,7 +10,11 @@ anywhere, blends, flips, the export resampler, every ending -- and each must giv
 
 (4 and 5 for the lists the band walk takes by rule: pipe_cases.band_eligible()), with the launch groups the restated
 planner expects and the runtime's pool back at its baseline.  A generated list the library refuses is a failure: of the
-generator, or a bug.  tests/test_pipe_cases.py checks the seed list's coverage and the reference without a GPU."""
+generator, or a bug.  tests/test_pipe_cases.py checks the seed list's coverage and the reference without a GPU.
+
+generate_scaled() gives the same for lists whose RGBA part runs at a region scale != 1 (a reduced-size export behind
+initialscale, or an RGBA frame at scale 0.5 / 2): the same walks, band eligibility from the exact halos; and the four fused
+pairs of the frame walk run once each at scale 0.5, with the launches read back so that a pair that fell back fails."""
 import ctypes as C
 
 import pytest
@@ -22,15 +26,14 @@ from ansel_amd import abi, lib
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("seed", pc.SEEDS)
-def test_generated_pipe(seed):
+def _every_walk(generate, seed):
     hc.hip()
-    host_nodes, src, tags = pc.generate(seed)
+    host_nodes, src, tags = generate(seed)
     what = "seed %d (%s)" % (seed, pc.describe(host_nodes))
     oracle = pc.oracle_chain(host_nodes, src)
     dev = pc.Tables(True)
     try:
-        nodes, _, dtags = pc.generate(seed, dev)
+        nodes, _, dtags = generate(seed, dev)
         assert [n.op for n in nodes] == [n.op for n in host_nodes] and dtags["bands"] == tags["bands"]
         base = pc.allocated()
         walks = [("module by module", pc.device_modulewise(nodes, src))]
@@ -47,6 +50,50 @@ def test_generated_pipe(seed):
         for name, got in walks:
             bad = pc.count_differing(got, oracle)
             assert bad == 0, "%s, %s: %d of %d words differ from the oracle" % (what, name, bad, oracle.size)
+    finally:
+        dev.release()
+
+
+@pytest.mark.parametrize("seed", pc.SEEDS)
+def test_generated_pipe(seed):
+    _every_walk(pc.generate, seed)
+
+
+@pytest.mark.parametrize("seed", pc.SCALED_SEEDS)
+def test_generated_pipe_at_a_region_scale(seed):
+    _every_walk(pc.generate_scaled, seed)
+
+
+@pytest.mark.parametrize("name", pc.SCALED_PAIRS)
+def test_fused_pairs_at_scale_one_half(name):
+    """denoise (profiled) + run, local contrast + run, diffuse + rgb_to_lab and non-local means -> local contrast with every
+    region at scale 0.5: the oracle's words with fusion on and off, and -- from the launch profile, as
+    tests/test_gpu_fused_variants.py reads it -- the pair in one launch, not its fallback"""
+    hc.hip()
+    host = dict((c[0], c) for c in pc.fused_pair_cases(pc.Tables(False), scale=0.5))[name]
+    _, host_nodes, kind, pairs, groups = host
+    assert pairs and all(n.piece.roi_in.scale == 0.5 and n.piece.roi_out.scale == 0.5 for n in host_nodes)
+    src = pc.pair_frame(kind)
+    oracle = pc.oracle_chain(host_nodes, src)
+    dev = pc.Tables(True)
+    try:
+        nodes = dict((c[0], c) for c in pc.fused_pair_cases(dev, scale=0.5))[name][1]
+        base = pc.allocated()
+        unfused, g0 = pc.device_pipe(nodes, src, fusion=False)
+        fused, g1 = pc.device_pipe(nodes, src, fusion=True)
+        assert (g0, g1) == (len(nodes), groups)
+        tags = pc.launch_tags(nodes, src)
+        assert pc.allocated() == base
+        assert pc.count_differing(unfused, oracle) == 0 and pc.count_differing(fused, oracle) == 0
+        chain = [t for t in tags if t.startswith("rgb_chain")]
+        if "denoiseprofile+run" in pairs:
+            assert "dn_finish_chain" in tags and not chain, tags
+        if "bilat+run" in pairs:
+            assert "bilat_splat" in tags and "bilat_slice" not in tags and chain, tags
+        if "diffuse+rgb_to_lab" in pairs:
+            assert "rgb_to_lab" not in tags, tags
+        if "nlmeans>bilat" in pairs:
+            assert "nlm_chunks" in tags and "bilat_splat" in tags, tags
     finally:
         dev.release()
 

@@ -256,6 +256,57 @@ def test_nlmeans_scaled():
     _exact(a, b, "nlmeans scale 0.5")
 
 
+def _scaled(w, h, s, **kw):
+    return abi.Piece.make(w, h, roi_in=abi.Roi.make(0, 0, w, h, s), roi_out=abi.Roi.make(0, 0, w, h, s), **kw)
+
+
+@pytest.mark.parametrize("scale", [2.0, 0.37])
+@pytest.mark.parametrize("radius", [1.0, 3.0])
+def test_nlmeans_at_further_scales(scale, radius):
+    """2.0: offsets of stride 2 up to 28, patch radius 2 / 6; 0.37: offsets -1 0 0 0 0 0 1 with their duplicates"""
+    w, h = 120, 90
+    img = _lab_image(w, h, 5)
+    a, b = _pair("nlmeans", _scaled(w, h, scale), abi.NlmeansData(radius, 50.0, 0.5, 1.0), img, img.shape)
+    _exact(a, b, "nlmeans scale %g" % scale)
+    one, _ = _pair("nlmeans", abi.Piece.make(w, h), abi.NlmeansData(radius, 50.0, 0.5, 1.0), img, img.shape)
+    assert not np.array_equal(a, one)
+
+
+@pytest.mark.parametrize("scale", [0.5, 2.0])
+@pytest.mark.parametrize("over", [dict(), dict(radius=2.0, nbhood=5.0, scattering=0.6, central_pixel_weight=0.5)])
+def test_denoiseprofile_nlmeans_scaled(over, scale):
+    """P, K, the scattering derived from the scale and the centre weight follow min(scale, 1) (denoiseprofile.c:1599-1648)"""
+    w, h = 160, 131
+    img = _noisy(w, h, 23)
+    d = params.denoiseprofile(mode=abi.DT_HIP_DENOISEPROFILE_NLMEANS, **over)
+    a, b = _pair("denoiseprofile", _scaled(w, h, scale, processed_maximum=synth.WB_COEFFS), d, img, img.shape)
+    _exact(a, b, "denoiseprofile nlmeans scale %g" % scale)
+    one, _ = _pair("denoiseprofile", abi.Piece.make(w, h, processed_maximum=synth.WB_COEFFS), d, img, img.shape)
+    assert np.array_equal(a, one) == (scale > 1.0)
+
+
+@pytest.mark.parametrize("scale", [0.5, 2.0])
+@pytest.mark.parametrize("case", [0, 4])
+def test_denoiseprofile_wavelets_scaled(case, scale):
+    """the band count, p[i], the gain and the bias follow min(scale, 1); exact with the reference on one thread and the oracle
+    summing in its order (as test_denoiseprofile_wavelets)"""
+    w, h = 300, 200
+    img = _noisy(w, h, 11 + case)
+    d = params.denoiseprofile(**DENOISE_CASES[case])
+    r, o = ck.ref(), ck.oracle()
+    threads = r.ref_get_num_threads()
+    r.ref_set_num_threads(1)
+    try:
+        o.oracle_denoiseprofile_sum_order(1)
+        a, b = _pair("denoiseprofile", _scaled(w, h, scale, processed_maximum=synth.WB_COEFFS), d, img, img.shape)
+        one, _ = _pair("denoiseprofile", abi.Piece.make(w, h, processed_maximum=synth.WB_COEFFS), d, img, img.shape)
+    finally:
+        o.oracle_denoiseprofile_sum_order(0)
+        r.ref_set_num_threads(threads)
+    _exact(a, b, "denoiseprofile wavelets scale %g" % scale)
+    assert np.array_equal(a, one) == (scale > 1.0)
+
+
 @pytest.mark.parametrize("over", [dict(), dict(use_new_vst=False), dict(use_new_vst=False, fix=False),
                                   dict(radius=2.0, nbhood=5.0, scattering=0.6, central_pixel_weight=0.5, strength=1.3),
                                   dict(wb_adaptive=False, shadows=0.5, bias=-2.0, nbhood=3.0)])
@@ -334,6 +385,28 @@ def test_bilat_bilateral_grid(w, h, ss, sr, detail):
     # and with its default thread count the reference stays within rounding of that
     a2, _ = _pair("bilat", abi.Piece.make(w, h), d, img, img.shape)
     assert float(np.abs(a2[..., 0] - b[..., 0]).max()) < 1e-3
+
+
+@pytest.mark.parametrize("iscale", [1.0, 1.7])
+@pytest.mark.parametrize("scale", [0.5, 2.0])
+@pytest.mark.parametrize("ss", [8.0, 50.0])
+def test_bilat_bilateral_grid_scaled(ss, scale, iscale):
+    """sigma_s / (iscale / roi_in.scale) sizes the grid (bilat.c:339); exact on one thread"""
+    w, h = 300, 200
+    img = _lab_image(w, h, 29)
+    img[::7, ::5, 0] = -3.0
+    img[3::11, 2::9, 0] = 140.0
+    d = abi.BilatData.bilateral(ss, 25.0, 0.33, iscale=iscale)
+    r = ck.ref()
+    threads = r.ref_get_num_threads()
+    r.ref_set_num_threads(1)
+    try:
+        a, b = _pair("bilat", _scaled(w, h, scale), d, img, img.shape)
+        one, _ = _pair("bilat", abi.Piece.make(w, h), abi.BilatData.bilateral(ss, 25.0, 0.33), img, img.shape)
+    finally:
+        r.ref_set_num_threads(threads)
+    _exact(a, b, "bilat scale %g iscale %g" % (scale, iscale))
+    assert not np.array_equal(a, one)
 
 
 AMAZE_SIZES = [(300, 200), (517, 389), (401, 333), (160, 160), (130, 97), (273, 273), (64, 64), (47, 53)]
@@ -654,6 +727,25 @@ def test_develop_blend_feathering(name, d, kind, w, h):
         z = b.copy()
         assert ck.call(o, "oracle_develop_blend", piece, d2, np.ascontiguousarray(a), z) == 0
         _exact(y, z, name)
+
+
+SCALED_MASK_CASES = blend_cases.blur_cases() + FEATHER_CASES
+
+
+@pytest.mark.parametrize("scale", [0.5, 2.0])
+@pytest.mark.parametrize("name,d,kind", SCALED_MASK_CASES, ids=[c[0] for c in SCALED_MASK_CASES])
+def test_develop_blend_mask_blur_and_feathering_scaled(name, d, kind, scale):
+    """sigma = blur_radius * roi_out.scale (blend.c:871), the guided filter's window (int)(2 * feathering_radius * scale + .5), at
+    least 1 (:606-611)"""
+    w, h = 131, 67
+    a, b = blend_cases.images_for(kind, w, h, 81 if name.startswith("blur") else 83)
+    piece = _scaled(w, h, scale, channels=1 if kind == "raw" else 4)
+    x, y, one = b.copy(), b.copy(), b.copy()
+    assert ck.call(ck.ref(), "ref_develop_blend", piece, d, np.ascontiguousarray(a), x) == 0
+    assert ck.call(ck.oracle(), "oracle_develop_blend", piece, d, np.ascontiguousarray(a), y) == 0
+    _exact(x, y, "blend %s at %g" % (name, scale))
+    assert ck.call(ck.ref(), "ref_develop_blend", abi.Piece.make(w, h, channels=1 if kind == "raw" else 4), d, np.ascontiguousarray(a), one) == 0
+    assert np.array_equal(x.view(np.uint32), one.view(np.uint32)) == name.endswith("-ignored")
 
 
 def test_develop_blend_feathering_guided_by_a_larger_input_is_refused():

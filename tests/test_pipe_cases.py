@@ -15,7 +15,7 @@ import pytest
 
 import checkers as ck
 import pipe_cases as pc
-from ansel_amd import abi, lib, synth, tiled
+from ansel_amd import abi, lib, params, pipe, synth, tiled
 
 
 @functools.lru_cache(maxsize=None)
@@ -271,3 +271,184 @@ def test_pairwise_set_covers_every_pair_of_switch_values():
     for c in cases:
         nodes = pc.run_nodes_of(tb, **pc.pairwise_kwargs(c))
         assert pc.plan_groups(nodes) == [("rgb", 0, len(nodes))], [x.op for x in nodes]
+
+
+# ---- generate() is pinned; the lists at a region scale != 1 (generate_scaled()) ------------------------------------------------
+_PLAIN_DATA = ("exposure", "diffuse", "denoiseprofile", "nlmeans", "bilat", "flip", "finalscale", "rawprepare", "temperature",
+               "highlights", "demosaic", "export_rows")  # data that is literals, no pointer and no fitted curve
+
+
+def test_generate_gives_the_lists_it_gave_before_there_was_a_scaled_generator():
+    """the 72 lists of generate(), word for word: every op, every piece, the data that is plain numbers, the frame's format and
+    the tags -- one digest, taken before generate_scaled() and _Builder.scale existed"""
+    import hashlib
+    h = hashlib.sha256()
+    for seed in pc.SEEDS:
+        nodes, src, tags = pc.generate(seed)
+        h.update(("%d %s %s %s %s %s %s|" % (seed, src.shape, src.dtype, tags["bands"], tags["batch"], tags["start"], tags["end"])).encode())
+        for n in nodes:
+            h.update(n.op.encode())
+            h.update(bytes(n.piece))
+            if n.op in _PLAIN_DATA:
+                h.update(bytes(n.data))
+    assert len(pc.SEEDS) == 72
+    assert h.hexdigest() == "d2e5f74ac9e5e0c04bb51fe92bd8564a6305e2b9e0a6c0398c65eebf0a803a68"
+
+
+def _scale_of(n):
+    return (n.piece.roi_in.scale, n.piece.roi_out.scale)
+
+
+def _is_nlm(n):
+    return n.op == "nlmeans" or (n.op == "denoiseprofile" and n.data.mode in (abi.DT_HIP_DENOISEPROFILE_NLMEANS, abi.DT_HIP_DENOISEPROFILE_NLMEANS_AUTO))
+
+
+def test_coverage_of_the_scaled_seed_list():
+    """24 lists; both shapes; every scale of either shape; every stencil module, both modes of denoise (profiled), at a scale
+    != 1; at least four lists on row bands, one of them with non-local means or diffuse at scale 2; every piece behind the
+    resampler (every piece of an RGBA list) carries the list's scale on both regions"""
+    assert len(pc.SCALED_SEEDS) == 24
+    shapes, scales, stencils, band_lists, heavy_on_bands = set(), set(), set(), 0, 0
+    for seed in pc.SCALED_SEEDS:
+        nodes, src, tags = pc.generate_scaled(seed)
+        s = tags["scale"]
+        shapes.add(tags["shape"])
+        scales.add((tags["shape"], s))
+        ops = [n.op for n in nodes]
+        assert ("initialscale" in ops) == (tags["shape"] == "export") and "finalscale" not in ops and "flip" not in ops
+        k0 = ops.index("initialscale") + 1 if tags["shape"] == "export" else 0
+        assert all(_scale_of(n) == (1.0, 1.0) for n in nodes[:max(k0 - 1, 0)])
+        if k0:
+            assert _scale_of(nodes[k0 - 1]) == (1.0, s)
+        assert all(_scale_of(n) == (s, s) for n in nodes[k0:] if n.data is not None or n.op in ("export_u16", "export_u8")), (seed, ops)
+        for n in nodes[k0:]:
+            if n.op in ("nlmeans", "diffuse", "bilat"):
+                stencils.add(n.op)
+            elif n.op == "denoiseprofile":
+                stencils.add("denoiseprofile_nlm" if _is_nlm(n) else "denoiseprofile")
+        band_lists += bool(tags["bands"])
+        if tags["bands"] and s == 2.0 and any(n.op in ("nlmeans", "diffuse") for n in nodes):
+            heavy_on_bands += 1
+        if tags["shape"] == "rgba":
+            assert src.dtype == np.float32 and src.shape[2] == 4
+    assert shapes == {"export", "rgba"}
+    assert scales == {("export", s) for s in pc.EXPORT_SCALES} | {("rgba", s) for s in pc.RGBA_SCALES}, scales
+    assert stencils == {"nlmeans", "diffuse", "bilat", "denoiseprofile", "denoiseprofile_nlm"}, stencils
+    assert band_lists >= 4 and heavy_on_bands >= 1, (band_lists, heavy_on_bands)
+
+
+def _halo(n):
+    return lib.load().dt_hip_band_halo_rows(n.op.encode(), C.byref(n.piece), C.cast(C.byref(n.data), C.c_void_p), C.sizeof(n.data))
+
+
+def _restated_halo(n):
+    """nlmeans_core_halo_rows(): P + 1 + the largest shift + the chunk height - 1 (nlmeans_core.c:264-295 gives the height);
+    diffuse_halo_rows(): iterations * 3 * (2^scales - 1), the scale count by the oracle (pinned to diffuse.c:1005-1012)"""
+    s = n.piece.roi_in.scale
+    if _is_nlm(n):
+        reach = pc.nlmeans_figures(n.data.radius, s)[2] if n.op == "nlmeans" else pc.dn_nlmeans_figures(n.data, s)[2]
+        return reach + ck.oracle().oracle_nlmeans_slice_height(n.piece.roi_out.height) - 1
+    assert n.op == "diffuse", n.op
+    f = ck.oracle().oracle_diffuse_scales
+    f.restype = C.c_int
+    return max(int(n.data.iterations), 1) * 3 * ((1 << f(C.byref(n.piece), C.byref(n.data))) - 1)
+
+
+@pytest.mark.parametrize("scale", sorted(set(pc.EXPORT_SCALES + pc.RGBA_SCALES + (1.0, 1.5, 2.6))))
+def test_band_halo_rows_follow_the_scale(scale):
+    """dt_hip_band_halo_rows() against the plain restatement, at every scale the scaled lists use (and 1, 1.5, 2.6): every
+    parameter set of the generator's pools, on its RGBA frames"""
+    seen = set()
+    for w, h in pc.RGBA_FRAMES:
+        piece = abi.Piece.make(w, h, roi_in=abi.Roi.make(0, 0, w, h, scale), roi_out=abi.Roi.make(0, 0, w, h, scale))
+        cases = [("nlmeans", abi.NlmeansData(r, 50.0, 0.5, 1.0)) for r in (1.0, 2.0, 3.0)]
+        cases += [("denoiseprofile", params.denoiseprofile(mode=abi.DT_HIP_DENOISEPROFILE_NLMEANS, **o))
+                  for o in (dict(), dict(radius=2, nbhood=5, scattering=0.6, central_pixel_weight=0.5))]
+        cases += [("diffuse", params.diffuse(name, iscale=i, **over)) for name, over in pc.DIFFUSE.items() for i in (1.0, 1.7)]
+        for op, d in cases:
+            n = pipe.Node(op, d, piece)
+            assert _halo(n) == _restated_halo(n), (op, w, h, scale)
+            seen.add(_halo(n))
+    if scale == 2.0:
+        assert max(seen) > 93  # beyond stencil_halo_bound(): a band that fetched the scale-1 halo would be short
+
+
+@pytest.mark.parametrize("seed", pc.SCALED_SEEDS)
+def test_scaled_lists_bands_and_halos(seed):
+    """an eligible scaled list is planned for 2 and 3 bands and no band is shorter than the exact halo a stencil module asks of
+    it; the halo of every non-local-means and diffuse node is the restated one; the planner's groups hold no surprise"""
+    nodes, _, tags = pc.generate_scaled(seed)
+    w, h = nodes[0].piece.roi_out.width, nodes[0].piece.roi_out.height
+    for n in nodes:
+        if n.data is not None and (_is_nlm(n) or n.op == "diffuse"):
+            assert _halo(n) == _restated_halo(n) == pc.exact_halo(n), (seed, n.op)
+    assert tags["bands"] == (tags["shape"] == "rgba" and all(pc.band_eligible(nodes, k, pc.exact_halo) for k in (2, 3)))
+    if tags["bands"]:
+        assert tiled.pipe_demosaic_method(nodes) == -1
+        for n_bands in (2, 3):
+            bands = tiled.plan_bands(w, h, n_bands, -1)
+            assert [(b.row0, b.rows) for b in bands] == pc.band_rows(w, h, -1, n_bands)
+            for n in nodes:
+                halo = pc.exact_halo(n)
+                for k, b in enumerate(bands):
+                    assert k == 0 or min(halo, b.row0) <= bands[k - 1].rows, (n.op, halo, k)
+                    assert k + 1 == n_bands or min(halo, h - b.row0 - b.rows) <= bands[k + 1].rows, (n.op, halo, k)
+    kinds = {k for k, _, _ in pc.plan_groups(nodes)}
+    assert kinds <= {"single", "raw", "rgb"}
+
+
+@functools.lru_cache(maxsize=None)
+def _scaled_oracle(seed):
+    nodes, src, tags = pc.generate_scaled(seed)
+    return nodes, src, tags, pc.oracle_chain(nodes, src)
+
+
+@pytest.mark.parametrize("seed", pc.SCALED_SEEDS)
+def test_every_scaled_pipe_gives_a_picture_that_is_not_the_scale_one_picture(seed):
+    nodes, src, tags, out = _scaled_oracle(seed)
+    shape, dtype = pc.out_format(nodes)
+    assert out.shape == shape and out.dtype == dtype
+    unit = {np.dtype(np.uint16): 1.0, np.dtype(np.uint8): 255.0 / 65535.0, np.dtype(np.float32): 1.0 / 65535.0}[out.dtype]
+    assert _spread(out) > 100.0 * unit, _spread(out)
+    if tags["shape"] == "rgba":
+        # the same list with every region at scale 1: a stencil module that read no scale would give these words
+        ones = [pipe.Node(n.op, n.data, abi.Piece.from_buffer_copy(n.piece)) for n in nodes]
+        for n in ones:
+            n.piece.roi_in.scale = n.piece.roi_out.scale = 1.0
+        clamped = tags["scale"] > 1.0 and not any(n.op in ("nlmeans", "diffuse", "bilat") for n in nodes)  # denoise (profiled): min(scale, 1)
+        assert (pc.count_differing(pc.oracle_chain(ones, src), out) == 0) == clamped, seed
+
+
+@pytest.mark.parametrize("seed", pc.SCALED_SEEDS)
+def test_a_scaled_pipe_ends_in_words_its_modules_wrote(seed):
+    """the demosaic (and the local laplacian) leave the fourth channel of their output alone, as the reference does: a list
+    that carried it to its end would be compared in words that are whatever the buffers held before.  With every module's
+    output buffer full of NaN, or of a finite value, the list ends in the words it ends in over zeroed buffers"""
+    nodes, src, _, out = _scaled_oracle(seed)
+    assert pc.alpha_is_written(nodes), pc.describe(nodes)
+    for fill in (np.nan, 123.25):
+        assert pc.count_differing(pc.oracle_chain(nodes, src, fill=fill), out) == 0, (seed, fill)
+
+
+@pytest.mark.parametrize("seed", pc.SCALED_SEEDS)
+def test_scaled_pipe_oracle_equals_the_reference(seed, ref_lib):
+    nodes, src, _ = pc.generate_scaled(seed)
+    _nodes_equal_the_reference(nodes, src, "scaled seed %d" % seed)
+
+
+def test_scaled_fused_pairs_fuse_by_rule_and_equal_the_reference_where_it_is_built():
+    tb = pc.Tables(False)
+    cases = dict((c[0], c) for c in pc.fused_pair_cases(tb, scale=0.5))
+    ones = dict((c[0], c) for c in pc.fused_pair_cases(tb))
+    found = set()
+    for name in pc.SCALED_PAIRS:
+        _, nodes, kind, pairs, groups = cases[name]
+        assert all(_scale_of(n) == (0.5, 0.5) for n in nodes)
+        assert pc.fused_pairs(nodes) == pairs and len(pc.plan_groups(nodes)) == groups, name
+        found |= pairs
+        out = pc.oracle_chain(nodes, pc.pair_frame(kind))
+        assert _spread(out) > (100.0 if out.dtype == np.uint16 else 100.0 / 65535.0), name
+        assert pc.count_differing(out, pc.oracle_chain(ones[name][1], pc.pair_frame(kind))) != 0, name
+        if ck.ref() is not None:
+            _nodes_equal_the_reference(nodes, pc.pair_frame(kind), name + " at 0.5")
+    assert found == {"denoiseprofile+run", "bilat+run", "diffuse+rgb_to_lab", "nlmeans>bilat"}

@@ -8,6 +8,7 @@ expectation comes from the reference's code in oracle/_ref, the rest restates th
 import ctypes as C
 import math
 
+import numpy as np
 import pytest
 
 import checkers as ck
@@ -131,3 +132,120 @@ def test_demosaic_tiling(method, overlap, geq, smooth):
     assert t.factor == pytest.approx(2.0 + max(1.0 + (0.25 if geq else 0.0), 1.0 if smooth else 0.0))
     assert (t.overlap, t.xalign, t.yalign, t.maxbuf) == (overlap, 2, 2, 1.0)
     assert t.factor_cl == pytest.approx(1.25 + (0.25 if geq else 0.0)) and t.factor_cl < t.factor
+
+
+# ---- the callbacks at a region scale != 1: what the host sizes its tiles' overlap with on a scaled export ----------------------
+SCALES = [0.5, 1.0, 2.0]
+
+
+def _scaled(w, h, s):
+    return abi.Piece.make(w, h, channels=4, roi_in=abi.Roi.make(0, 0, w, h, s), roi_out=abi.Roi.make(0, 0, w, h, s))
+
+
+@pytest.mark.parametrize("scale", SCALES)
+@pytest.mark.parametrize("iscale", [1.0, 1.7])
+@pytest.mark.parametrize("preset,over", [("lens_deblur_soft", {}), ("default", dict(radius=16)), ("fast_local_contrast", {}),
+                                         ("inpaint_highlights", {})])
+def test_diffuse_tiling_follows_the_scale(preset, over, iscale, scale):
+    # diffuse.c:256-296: zoom = iscale / roi_in.scale, final_radius = (radius + radius_center) * 2 / zoom, scales by
+    # num_steps_to_reach_equivalent_sigma(B_SPLINE_SIGMA, final_radius) in [1, 10] -- sigma_n = sqrt(2)^... restated below
+    d = params.diffuse(preset, iscale=iscale, **over)
+    p = _scaled(640, 480, scale)
+    t = _t("dt_hip_iop_diffuse_tiling", p, d)
+    zoom = np.float32(float(np.float32(iscale)) / scale)
+    final = np.float32(d.radius + d.radius_center) * np.float32(2.0) / zoom
+    # bspline.h: s = 0, radius = sigma; while radius < sigma_final: s++, radius = sqrt(radius^2 + (2^s sigma)^2)
+    sigma = np.float32(1.0553651328015339)
+    s, radius = 0, sigma
+    while radius < final:
+        s += 1
+        radius = np.sqrt(radius * radius + (np.float32(1 << s) * sigma) ** 2, dtype=np.float32)
+    scales = min(max(s + 1, 1), 10)
+    l = ck.oracle()
+    if l is not None:
+        l.oracle_diffuse_scales.restype = C.c_int
+        assert scales == l.oracle_diffuse_scales(C.byref(p), C.byref(d))
+    assert t.overlap == 1 << scales
+    assert t.factor == pytest.approx(6.0625 + scales) and (t.xalign, t.yalign) == (1, 1)
+
+
+@pytest.mark.parametrize("scale", SCALES)
+@pytest.mark.parametrize("iscale", [1.0, 1.7])
+@pytest.mark.parametrize("sigma_s", [8.0, 50.0])
+def test_bilat_tiling_bilateral_follows_the_scale(sigma_s, iscale, scale):
+    # bilat.c:259-279: sigma_s / (iscale / roi_in.scale) is the grid's sigma and a quarter of the overlap
+    w, h = 640, 480
+    d = abi.BilatData.bilateral(sigma_s, 25.0, 0.33, iscale=iscale)
+    p = _scaled(w, h, scale)
+    t = _t("dt_hip_iop_bilat_tiling", p, d)
+    sig = np.float32(sigma_s) / np.float32(float(np.float32(iscale)) / scale)
+    assert t.overlap == math.ceil(np.float32(4) * sig)
+    l = ck.oracle()
+    if l is None:
+        pytest.skip("oracle/liboracle.so not built")
+    dims = (C.c_int * 3)()
+    sg = (C.c_float * 2)()
+    l.oracle_bilat_grid(C.byref(p), C.byref(d), dims, sg)
+    grid = dims[0] * dims[1] * dims[2] * 4
+    base = 16.0 * w * h
+    assert t.factor == pytest.approx(2.0 + 2.0 * grid / base, rel=1e-6) and t.factor_cl == pytest.approx(t.factor, rel=1e-6)
+    assert t.maxbuf == pytest.approx(max(1.0, grid / base), rel=1e-6)
+    if scale != 1.0 or iscale != 1.0:
+        l.oracle_bilat_grid(C.byref(abi.Piece.make(w, h, channels=4)), C.byref(abi.BilatData.bilateral(sigma_s, 25.0, 0.33)), dims, sg)
+        assert dims[0] * dims[1] * dims[2] * 4 != grid
+
+
+@pytest.mark.parametrize("scale", SCALES)
+@pytest.mark.parametrize("radius,nbhood,scattering", [(1.0, 7.0, 0.0), (2.0, 5.0, 0.4), (1.0, 9.0, 1.0)])
+def test_denoiseprofile_nlmeans_tiling_follows_the_scale(radius, nbhood, scattering, scale):
+    # denoiseprofile.c:801-814: scale = min(min(roi_in.scale, 2), 1), P = ceil(radius scale), K = ceil(nbhood scale)
+    d = params.denoiseprofile(mode=abi.DT_HIP_DENOISEPROFILE_NLMEANS, radius=radius, nbhood=nbhood, scattering=scattering)
+    t = _t("dt_hip_iop_denoiseprofile_tiling", _scaled(640, 480, scale), d)
+    s = np.float32(min(min(scale, 2.0), 1.0))
+    P, K = math.ceil(np.float32(radius) * s), math.ceil(np.float32(nbhood) * s)
+    ks = math.ceil(float(np.float32(scattering)) * (K * K * K + 7.0 * K * math.sqrt(K)) / 6.0) + K
+    assert t.overlap == P + ks
+    assert t.factor == 2.25 and t.factor_cl == 3.0
+
+
+@pytest.mark.parametrize("scale", SCALES)
+@pytest.mark.parametrize("w,h", [(6000, 4000), (640, 480), (400, 300)])
+def test_denoiseprofile_wavelets_tiling_follows_the_scale(w, h, scale):
+    # denoiseprofile.c:815-846 with the band loop of :1301-1317, where a band's support is measured in input pixels:
+    # supp_in = supp / min(scale, 1)
+    d = params.denoiseprofile()
+    p = _scaled(w, h, scale)
+    t = _t("dt_hip_iop_denoiseprofile_tiling", p, d)
+    in_scale = np.float32(min(scale, 1.0))
+    supp0 = min(np.float32(2 * (2 << 6) + 1), np.float32(max(w, h)) * np.float32(0.2))
+    i0 = np.log2((supp0 - np.float32(1)) * np.float32(0.5))
+    bands = 0
+    while bands < 7:
+        supp_in = np.float32(2 * (2 << bands) + 1) * (np.float32(1) / in_scale)
+        i_in = np.log2((supp_in - np.float32(1)) * np.float32(0.5)) - np.float32(1)
+        if np.float32(1) - (i_in + np.float32(0.5)) / i0 < 0:
+            break
+        bands += 1
+    l = ck.oracle()
+    if l is not None:
+        l.oracle_denoiseprofile_bands.restype = C.c_int
+        assert bands == l.oracle_denoiseprofile_bands(C.byref(p), C.byref(d))
+    assert t.overlap == 1 << bands and t.factor == 5.0 and t.factor_cl == pytest.approx(3.0 + bands + 1.0 / 64.0)
+    if scale == 0.5:
+        assert bands == _bands_at_one(w, h) - 1  # log2 of the support grows by one: one band fewer
+
+
+def _bands_at_one(w, h):
+    d = params.denoiseprofile()
+    return int(math.log2(_t("dt_hip_iop_denoiseprofile_tiling", abi.Piece.make(w, h, channels=4), d).overlap))
+
+
+@pytest.mark.parametrize("scale", SCALES)
+def test_default_tiling_reads_no_scale(scale):
+    # tiling.c:1423-1463 sizes the default from the two regions' areas alone; the blend stage has no tiling callback of its
+    # own in the C-ABI (its mask blur and feathering make the host plan it untiled), so there is no blend-bearing default
+    l = lib.load()
+    t, one = abi.Tiling(), abi.Tiling()
+    l.dt_hip_default_tiling(C.byref(_scaled(640, 480, scale)), 0, C.byref(t))
+    l.dt_hip_default_tiling(C.byref(abi.Piece.make(640, 480, channels=4)), 0, C.byref(one))
+    assert bytes(t) == bytes(one)
