@@ -702,3 +702,36 @@ extern "C" int dt_hip_export_png(int devid, int width, int height, const dt_hip_
   release();
   return check_launch("export_png");
 }
+
+// tests only (not in include/ansel_hip.h): png_tables alone on caller-supplied histograms -- nseg x (PD_NLIT + PD_NDIST)
+// host counts for a stream of nbytes bytes -- and the pd_seg_t records copied back to segs_out (the Adler sums are not
+// set); at most 65536 histograms a call.  tests/native/png_host.cpp png_host_tables() is its twin with one lane.
+extern "C" size_t dt_hip_test_png_sizeof_seg(void) { return sizeof(pd_seg_t); }
+
+extern "C" int dt_hip_test_png_tables(int devid, const uint32_t *freq, uint64_t nbytes, int nseg, int level, void *segs_out)
+{
+  if(!valid_device(devid) || !freq || !segs_out || nseg < 1 || nseg > 65536 || level < 0 || level > 9) return DT_HIP_INVALID_ARG;
+  if(nbytes <= (uint64_t)(nseg - 1) * PD_SEG || nbytes > (uint64_t)nseg * PD_SEG) return DT_HIP_INVALID_ARG;
+  const size_t sz_freq = (size_t)nseg * NSYM * 4, sz_segs = (size_t)nseg * sizeof(pd_seg_t);
+  dt_hip_mem_t m_freq = dt_hip_alloc_device_buffer(devid, sz_freq);
+  dt_hip_mem_t m_segs = dt_hip_alloc_device_buffer(devid, sz_segs);
+  int err = (m_freq && m_segs) ? DT_HIP_SUCCESS : DT_HIP_DEFAULT_ERROR;
+  if(err == DT_HIP_SUCCESS) err = dt_hip_write_buffer_to_device(devid, freq, m_freq, 0, sz_freq, 1);
+  if(err == DT_HIP_SUCCESS)
+  {
+    hipStream_t s = stream_of(devid);
+    if(hipMemsetAsync(m_segs, 0, sz_segs, s) != hipSuccess) err = DT_HIP_DEFAULT_ERROR;
+  }
+  if(err == DT_HIP_SUCCESS)
+  {
+    {
+      launch_scope ls(devid, "png_tables");
+      png_tables<<<(unsigned)nseg, 64, 0, stream_of(devid)>>>((const uint32_t *)m_freq, nbytes, level, (pd_seg_t *)m_segs);
+    }
+    err = check_launch("test_png_tables");
+  }
+  if(err == DT_HIP_SUCCESS) err = dt_hip_read_buffer_from_device(devid, segs_out, m_segs, 0, sz_segs, 1);
+  if(m_freq) dt_hip_release_mem_object(m_freq);
+  if(m_segs) dt_hip_release_mem_object(m_segs);
+  return err;
+}

@@ -295,10 +295,11 @@ PD_FN void pd_rle(const uint8_t *len, int nlit, int ndist, F emit)
 }
 
 // the code lengths of one alphabet from its counts (at least two symbols get a code: zero counts are raised to 1 from
-// symbol 0 up, so that every code is complete); lane / nlanes / wave_min / sync as jh_build()
+// symbol 0 up, so that every code is complete); lane / nlanes / wave_min / sync as jh_build().  longest (tests; the
+// kernels pass none): the longest code length before the Annex K.3 adjustment
 template <class WaveMin, class Sync>
 PD_FN void pd_lengths(jh_work_t *w, const uint32_t *freq, int n, int limit, int lane, int nlanes, WaveMin wave_min,
-                      Sync sync, uint8_t *bits, uint16_t *vals, uint8_t *len_out)
+                      Sync sync, uint8_t *bits, uint16_t *vals, uint8_t *len_out, int *longest = nullptr)
 {
   if(lane == 0)
   {
@@ -324,6 +325,12 @@ PD_FN void pd_lengths(jh_work_t *w, const uint32_t *freq, int n, int limit, int 
     for(int l = 1; l <= limit; l++)
       for(int k = 0; k < bits[l - 1]; k++) len_out[vals[p++]] = (uint8_t)l;
     (void)nv;
+    if(longest)
+    {
+      *longest = 0;
+      for(int i = 0; i < n; i++)
+        if(w->codesize[i] > *longest) *longest = w->codesize[i];
+    }
   }
   sync();
 }
@@ -338,10 +345,12 @@ struct pd_tab_work_t
 };
 
 // the block of one segment from its symbol counts (freq: PD_NLIT literal / length, then PD_NDIST distance counts; the
-// stream's byte count nbytes; level 0: stored).  Fills every field of *seg but the Adler sums.
+// stream's byte count nbytes; level 0: stored).  Fills every field of *seg but the Adler sums.  longest (tests; the
+// kernels pass none): three words, the longest unadjusted code length of the literal / length, distance and code
+// length alphabets (pd_lengths())
 template <class WaveMin, class Sync>
 PD_FN void pd_tables(pd_tab_work_t *tw, const uint32_t *freq, uint32_t nbytes, int level, int lane, int nlanes,
-                     WaveMin wave_min, Sync sync, pd_seg_t *seg)
+                     WaveMin wave_min, Sync sync, pd_seg_t *seg, int *longest = nullptr)
 {
   if(level == 0)
   {
@@ -354,9 +363,10 @@ PD_FN void pd_tables(pd_tab_work_t *tw, const uint32_t *freq, uint32_t nbytes, i
     }
     return;
   }
-  pd_lengths(&tw->w, freq, PD_NLIT, 15, lane, nlanes, wave_min, sync, tw->bits, tw->vals, seg->len);
+  pd_lengths(&tw->w, freq, PD_NLIT, 15, lane, nlanes, wave_min, sync, tw->bits, tw->vals, seg->len,
+             longest);
   pd_lengths(&tw->w, freq + PD_NLIT, PD_NDIST, 15, lane, nlanes, wave_min, sync, tw->bits, tw->vals,
-             seg->len + PD_NLIT);
+             seg->len + PD_NLIT, longest ? longest + 1 : nullptr);
   uint32_t nlit = PD_NLIT, ndist = PD_NDIST;
   if(lane == 0)
   {
@@ -366,7 +376,8 @@ PD_FN void pd_tables(pd_tab_work_t *tw, const uint32_t *freq, uint32_t nbytes, i
     pd_rle(seg->len, (int)nlit, (int)ndist, [&](int s, uint32_t, int) { tw->clfreq[s]++; });
   }
   sync();
-  pd_lengths(&tw->w, tw->clfreq, PD_NCL, 7, lane, nlanes, wave_min, sync, tw->bits, tw->vals, seg->cl_len);
+  pd_lengths(&tw->w, tw->clfreq, PD_NCL, 7, lane, nlanes, wave_min, sync, tw->bits, tw->vals, seg->cl_len,
+             longest ? longest + 2 : nullptr);
   if(lane == 0)
   {
     uint32_t ncl = PD_NCL;

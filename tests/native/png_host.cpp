@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "png_deflate.h"
@@ -56,8 +57,22 @@ struct bitwriter_t
   void align() { pos = (pos + 7) & ~(uint64_t)7; b.resize(pos >> 3); }
 };
 
+// what the last encode did, as JSON (png_host_stats()): the tests' proof that a frame reached a branch
+std::string g_stats;
+
+void js(std::string &o, const char *key, uint64_t v) { o += "\"" + std::string(key) + "\":" + std::to_string(v) + ","; }
+
+template <class T>
+void js_list(std::string &o, const char *key, const T *v, int n)
+{
+  o += "\"" + std::string(key) + "\":[";
+  for(int i = 0; i < n; i++) o += std::to_string((unsigned)v[i]) + (i + 1 < n ? "," : "");
+  o += "],";
+}
+
 std::vector<uint8_t> zlib_stream(const std::vector<uint8_t> &fs, int level)
 {
+  g_stats = "{\"blocks\":[";
   const uint64_t N = fs.size();
   const uint64_t nseg = (N + PD_SEG - 1) / PD_SEG;
   const uint8_t *s = fs.data();
@@ -75,6 +90,7 @@ std::vector<uint8_t> zlib_stream(const std::vector<uint8_t> &fs, int level)
     std::fill(tok.begin(), tok.end(), 0);
     std::fill(mat.begin(), mat.end(), 0);
     uint32_t freq[PD_NLIT + PD_NDIST] = { 0 };
+    uint64_t refused = ~0ull;
     if(level > 0)
     {
       const uint64_t ws = s0 > PD_WIN ? s0 - PD_WIN : 0;
@@ -86,6 +102,16 @@ std::vector<uint8_t> zlib_stream(const std::vector<uint8_t> &fs, int level)
         for(uint64_t p = std::max(c, s0); p < e; p++)
           lenv[p - s0] = pd_best(s, N, p, ws, (uint32_t)std::min<uint64_t>(PD_MAXLEN, s1 - p),
                                  [&](uint32_t slot) { return head[slot]; }, &distv[p - s0]);
+        for(uint64_t p = std::max(c, s0); p < e; p++) // stats: the nearest 3-byte match refused as too far
+          for(int t = 0; t < PD_NTAB && pd_keyed(p, N, t); t++)
+          {
+            const int32_t q = head[pd_slot(s, p, t)];
+            if(q < 0) continue;
+            const uint64_t d = p - ws - (uint64_t)q;
+            uint32_t l = 0;
+            while(l < 4 && l < s1 - p && s[ws + q + l] == s[p + l]) l++;
+            if(l == 3 && d > PD_TOO_FAR && d <= PD_WIN) refused = std::min(refused, d);
+          }
         for(uint64_t p = c; p < e; p++)
           for(int t = 0; t < PD_NTAB && pd_keyed(p, N, t); t++)
           {
@@ -120,9 +146,57 @@ std::vector<uint8_t> zlib_stream(const std::vector<uint8_t> &fs, int level)
       freq[256]++;
     }
     pd_seg_t seg;
-    pd_tables(&tw, freq, (uint32_t)n, level, 0, 1, [](uint64_t v) { return v; }, []() {}, &seg);
+    int longest[3] = { 0, 0, 0 };
+    pd_tables(&tw, freq, (uint32_t)n, level, 0, 1, [](uint64_t v) { return v; }, []() {}, &seg, longest);
     const bool last = k + 1 == nseg;
     const uint64_t start = bw.pos;
+    {
+      std::string &o = g_stats;
+      o += k ? ",{" : "{";
+      js(o, "type", seg.type);
+      js(o, "nbytes", n);
+      js(o, "phase", start & 7);
+      js(o, "bits", seg.bits);
+      uint32_t nm = 0, lmin = ~0u, lmax = 0, dmin = ~0u, dmax = 0, far3 = 0, used = 0;
+      for(uint64_t i = 0; i < n; i++)
+        if(mat[i])
+        {
+          nm++;
+          lmin = std::min(lmin, lenv[i]);
+          lmax = std::max(lmax, lenv[i]);
+          dmin = std::min(dmin, distv[i]);
+          dmax = std::max(dmax, distv[i]);
+          if(lenv[i] == 3) far3 = std::max(far3, distv[i]);
+        }
+      for(int i = 0; i < PD_NDIST; i++) used += freq[PD_NLIT + i] != 0;
+      js(o, "matches", nm);
+      js(o, "len_min", nm ? lmin : 0);
+      js(o, "len_max", lmax);
+      js(o, "dist_min", nm ? dmin : 0);
+      js(o, "dist_max", dmax);
+      js(o, "far3_taken", far3);
+      js(o, "far3_refused", refused == ~0ull ? 0 : refused);
+      js(o, "dist_used", used);
+      if(level > 0)
+      {
+        js_list(o, "longest", longest, 3);
+        js(o, "nlit", seg.nlit);
+        js(o, "ndist", seg.ndist);
+        js(o, "ncl", seg.ncl);
+      }
+      if(seg.type == PD_DYNAMIC)
+      {
+        js_list(o, "len", seg.len, PD_NLIT + PD_NDIST);
+        js_list(o, "cl_len", seg.cl_len, PD_NCL);
+        std::vector<uint32_t> r;
+        pd_rle(seg.len, (int)seg.nlit, (int)seg.ndist, [&](int sym, uint32_t extra, int) {
+          r.push_back((uint32_t)sym);
+          r.push_back(extra);
+        });
+        js_list(o, "rle", r.data(), (int)r.size());
+      }
+      o += "\"last\":" + std::to_string(last ? 1 : 0) + "}";
+    }
     if(seg.type == PD_STORED)
     {
       bw.put(last ? 1 : 0, 3);
@@ -168,6 +242,12 @@ std::vector<uint8_t> zlib_stream(const std::vector<uint8_t> &fs, int level)
   bw.put(b & 255, 8);
   bw.put(a >> 8, 8);
   bw.put(a & 255, 8);
+  const uint64_t zlen = bw.b.size(), nidat = (zlen + PD_IDAT - 1) / PD_IDAT;
+  g_stats += "],";
+  js(g_stats, "N", N);
+  js(g_stats, "zlen", zlen);
+  js(g_stats, "nidat", nidat);
+  g_stats += "\"last_idat\":" + std::to_string(zlen - (nidat - 1) * PD_IDAT) + "}";
   return bw.b;
 }
 
@@ -197,3 +277,45 @@ extern "C" size_t png_host_encode(const void *in, int w, int h, int depth, int l
 }
 
 extern "C" void png_host_copy(uint8_t *out) { memcpy(out, g_out.data(), g_out.size()); }
+
+// what the last png_host_encode() did, as JSON: per block its type, bytes, the bit phase it started at, its matches'
+// shortest / longest length and distance, the farthest 3-byte match taken and the nearest one refused, the distance
+// codes used, the longest unadjusted code length of the three alphabets, and of a dynamic block HLIT / HDIST / HCLEN's
+// counts, the code lengths and what pd_rle() coded (symbol, extra, ...); then N, zlen, the IDAT count and the last
+// chunk's bytes.  Returns the length; out may be null
+extern "C" size_t png_host_stats(char *out)
+{
+  if(out) memcpy(out, g_stats.data(), g_stats.size());
+  return g_stats.size();
+}
+
+// pd_rle() alone: len is PD_NLIT + PD_NDIST code lengths; out takes (symbol, extra) pairs; returns their count
+extern "C" size_t png_host_rle(const uint8_t *len, int nlit, int ndist, uint32_t *out)
+{
+  size_t k = 0;
+  pd_rle(len, nlit, ndist, [&](int sym, uint32_t extra, int) {
+    out[2 * k] = (uint32_t)sym;
+    out[2 * k + 1] = extra;
+    k++;
+  });
+  return k;
+}
+
+// pd_tables() with one lane on nseg histograms of PD_NLIT + PD_NDIST counts (a stream of nbytes bytes: every segment
+// PD_SEG but the last): the twin of dt_hip_test_png_tables() in png.hip; longest (may be null) takes three words per
+// segment
+extern "C" size_t png_host_sizeof_seg(void) { return sizeof(pd_seg_t); }
+
+extern "C" void png_host_tables(const uint32_t *freq, uint64_t nbytes, int nseg, int level, void *segs_out, int *longest)
+{
+  static pd_tab_work_t tw;
+  for(int k = 0; k < nseg; k++)
+  {
+    pd_seg_t seg;
+    memset(&seg, 0, sizeof(seg));
+    const uint64_t s0 = (uint64_t)k * PD_SEG;
+    pd_tables(&tw, freq + (size_t)k * (PD_NLIT + PD_NDIST), (uint32_t)(std::min(nbytes, s0 + PD_SEG) - s0), level, 0, 1, [](uint64_t v) { return v; }, []() {},
+              &seg, longest ? longest + 3 * k : nullptr);
+    memcpy((char *)segs_out + (size_t)k * sizeof(seg), &seg, sizeof(seg));
+  }
+}

@@ -5,7 +5,13 @@
   * its inflated IDAT equals libpng's filtered stream, and libpng decodes the input's pixels from it
   * the same frame twice gives the same bytes
   * capacity exactly 8 + L succeeds; one byte less gives the length word UINT64_MAX and leaves the bytes behind the
-    capacity untouched"""
+    capacity untouched; the same with a second IDAT chunk of one byte
+  * the designed corpus png_ref.edge_frames() (tests/test_png_host.py shows on the host build which branch of the
+    encoder each entry reaches): the device file equals the host build's, inflates to the filtered stream and decodes
+    in libpng; the two png_scan frames (257 and 513 segments: 2 and 3 a thread, stored and dynamic blocks inside one
+    thread's group) and the all-0xFF frame twice with identical bytes
+  * png_tables alone (dt_hip_test_png_tables()) on histograms no frame produces: the 64-lane record equals the one-lane
+    host build's, the Kraft sum is 1 and the cost optimal within the limit, all three length limits engaged"""
 import ctypes as C
 
 import numpy as np
@@ -116,3 +122,67 @@ def test_refused_arguments():
     assert "4 x 0" in l.dt_hip_last_error().decode()
     d_in.release()
     d_out.release()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the designed corpus (png_ref.edge_frames(); tests/test_png_host.py proves on the host build which branch each reaches)
+
+EDGES = pr.edge_frames()
+
+
+@pytest.mark.parametrize("name,levels,feats", EDGES, ids=[e[0] for e in EDGES])
+def test_edge_frame_device_file_equals_host_build(name, levels, feats):
+    img = pr.edge_frame(name)
+    h, w = img.shape[:2]
+    for level in levels:
+        want, _, stream = pr.edge_host(name, level)
+        got = encode_dev(img, level)
+        assert got == want, level
+        assert pr.inflate(got) == stream, level
+        if pr.ref() is not None:
+            rgb, _, _ = pr.libpng_read(got, w, h, 8 * img.itemsize)
+            assert np.array_equal(rgb, img[..., :3]), level
+        if name in pr.SCAN_FRAMES or name == "all_ff":
+            assert encode_dev(img, level) == got, level
+
+
+def test_capacity_one_byte_short_at_an_idat_boundary():
+    """zlen 65537: the second IDAT chunk holds one byte, the Adler-32's last"""
+    img = pr.edge_frame("zlen_65537")
+    exact = encode_dev(img, 0)
+    assert exact == pr.edge_host("zlen_65537", 0)[0]
+    n, buf = encode_dev(img, 0, capacity=8 + len(exact), raw=True)
+    assert n == len(exact) and buf[8:8 + n].tobytes() == exact
+    assert (buf[8 + n:] == 0xA5).all()
+    n, buf = encode_dev(img, 0, capacity=8 + len(exact) - 1, raw=True)
+    assert n == 2 ** 64 - 1
+    assert (buf[8:] == 0xA5).all()
+
+
+def test_table_builder_device_equals_host_and_holds_the_code_properties():
+    """png_tables alone (dt_hip_test_png_tables()) on png_ref.table_histograms(): each record equals the one-lane host
+    build's in every field but the Adler sums -- the 64-lane minimum search breaks ties as the one-lane order does, on
+    Fibonacci counts too -- and png_ref.check_tables() holds for the device's record: codes within 15 / 15 / 7 bits, the
+    Kraft sum exactly 1, the cost optimal wherever the unadjusted code fits the limit, the block's bits recomputed"""
+    l = hc.hip()
+    l.dt_hip_test_png_sizeof_seg.restype = C.c_size_t
+    assert l.dt_hip_test_png_sizeof_seg() == C.sizeof(pr.Seg)
+    l.dt_hip_test_png_tables.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]
+    names, freq = pr.table_histograms()
+    n = len(freq)
+    host_segs, longest = pr.host_tables(freq)
+    segs = (pr.Seg * n)()
+    rc = l.dt_hip_test_png_tables(0, freq.ctypes.data, n * pr.SEG, n, 5, C.byref(segs))
+    assert rc == abi.DT_HIP_SUCCESS, l.dt_hip_last_error().decode()
+    for name, f, s, hs, lg in zip(names, freq, segs, host_segs, longest):
+        assert pr.seg_fields(s) == pr.seg_fields(hs), name
+        pr.check_tables(f, s, lg)
+    stored = (pr.Seg * 3)()
+    rc = l.dt_hip_test_png_tables(0, freq.ctypes.data, 3 * pr.SEG, 3, 0, C.byref(stored))
+    assert rc == abi.DT_HIP_SUCCESS
+    assert all(pr.seg_fields(s) == (0, pr.SEG, 0, 0, 0, 0, bytes(316), bytes(19)) for s in stored)
+    assert l.dt_hip_test_png_tables(0, freq.ctypes.data, 3 * pr.SEG + 1, 3, 5, C.byref(segs)) == abi.DT_HIP_INVALID_ARG
+    assert l.dt_hip_test_png_tables(0, freq.ctypes.data, 65537 * pr.SEG, 65537, 5, C.byref(segs)) == abi.DT_HIP_INVALID_ARG
+    by = dict(zip(names, segs))
+    for name in pr.LARGE_FEW_SYMBOLS:  # the dynamic block wins: check_tables() saw the lengths pd_lengths() raised
+        assert by[name].type == 2, name
