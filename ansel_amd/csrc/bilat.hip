@@ -452,19 +452,21 @@ int bilat_splat_rows(int devid, const grid_t &b, float *buf, const float4 *in_ro
   static const bool v1 = getenv("ANSEL_HIP_BILAT_SPLAT_V1") != nullptr; // the first gather, for A/B timing
   if(v1)
   {
-    float *L = (float *)dt_hip_alloc_device_buffer(devid, n * sizeof(float));
-    if(!L) return DT_HIP_SYSMEM_ALLOCATION;
+    const dev_buf_t L_buf = dev_buf_t::alloc(devid, n * sizeof(float)); // (its release is stream-ordered)
+    if(!L_buf) return DT_HIP_SYSMEM_ALLOCATION;
+    float *const L = L_buf.as<float>();
     {
       launch_scope ls(devid, "bilat_splat");
       bilat_lightness<<<stream_grid(n, 256), 256, 0, s>>>(in_rows, L, n);
       bilat_splat<<<(nodes + SPLAT_THREADS - 1) / SPLAT_THREADS, SPLAT_THREADS, (size_t)b.size_z * SPLAT_THREADS * sizeof(float), s>>>(
           L, buf, b, row_lo, row_hi, accumulate);
     }
-    dt_hip_release_mem_object(L); // stream-ordered
     return DT_HIP_SUCCESS;
   }
 #endif
-  float2 *zc = zc_pre ? const_cast<float2 *>(zc_pre) : (float2 *)dt_hip_alloc_device_buffer(devid, n * sizeof(float2));
+  // the caller's cells or ours (whose release is stream-ordered)
+  const dev_buf_t zc_buf = zc_pre ? dev_buf_t::borrow(const_cast<float2 *>(zc_pre)) : dev_buf_t::alloc(devid, n * sizeof(float2));
+  float2 *const zc = zc_buf.as<float2>();
   if(!zc) return DT_HIP_SYSMEM_ALLOCATION;
   {
     launch_scope ls(devid, "bilat_splat");
@@ -487,7 +489,6 @@ int bilat_splat_rows(int devid, const grid_t &b, float *buf, const float4 *in_ro
       else bilat_splat2<false, false><<<grid, SPLAT_THREADS, cells, s>>>(zc, buf, b, row_lo, row_hi, accumulate);
     }
   }
-  if(!zc_pre) dt_hip_release_mem_object(zc); // stream-ordered
   return DT_HIP_SUCCESS;
 }
 
@@ -495,14 +496,15 @@ int bilat_splat_rows(int devid, const grid_t &b, float *buf, const float4 *in_ro
 // fused launch leaves it in a second grid the slice reads (buf keeps the splat); a grid of more than BLUR_FUSED_CELLS cells takes
 // its x-pass in a launch of its own (second grid), and the y- and z-passes bring it back into buf
 constexpr size_t BLUR_FUSED_CELLS = (size_t)1 << 22;
-// the blur: *blurred = the grid that holds it (buf or *second), *second = the grid to release once nothing reads `blurred` any more
-int bilat_blur(int devid, const grid_t &b, float *buf, const float **blurred, float **second_out)
+// the blur: *blurred = the grid that holds it (buf or second_buf), second_buf = the grid to let go once nothing reads `blurred` any
+// more (stream-ordered)
+int bilat_blur(int devid, const grid_t &b, float *buf, const float **blurred, dev_buf_t &second_buf)
 {
   hipStream_t s = stream_of(devid);
   const size_t cells = (size_t)b.size_x * b.size_y * b.size_z;
-  float *const second = (float *)dt_hip_alloc_device_buffer(devid, cells * sizeof(float));
+  second_buf = dev_buf_t::alloc(devid, cells * sizeof(float));
+  float *const second = second_buf.as<float>();
   if(!second) return DT_HIP_SYSMEM_ALLOCATION;
-  *second_out = second;
   launch_scope ls(devid, "bilat_blur");
   // z-lines per workgroup: ~2048 cells (eight per lane), whole lines
   const int npw = b.size_z >= 2048 ? 1 : 2048 / b.size_z;
@@ -526,15 +528,14 @@ int bilat_blur_and_slice(int devid, const grid_t &b, float *buf, const dt_hip_bi
 {
   hipStream_t s = stream_of(devid);
   const float *blurred = nullptr;
-  float *second = nullptr;
-  const int berr = bilat_blur(devid, b, buf, &blurred, &second);
+  dev_buf_t second;
+  const int berr = bilat_blur(devid, b, buf, &blurred, second);
   if(berr != DT_HIP_SUCCESS) return berr;
   {
     const float norm = -d->detail * b.sigma_r * 0.04f;
     launch_scope ls(devid, "bilat_slice");
     bilat_slice<<<stream_grid((size_t)b.width * rows, 256), 256, 0, s>>>(in_rows, out_rows, blurred, b, norm, row0, rows);
   }
-  dt_hip_release_mem_object(second); // stream-ordered
   return check_launch("bilat");
 }
 } // namespace
@@ -608,11 +609,11 @@ int bilat_process_cells(int devid, const dt_hip_piece_t *piece, const dt_hip_bil
   grid_t b;
   if(bilat_grid_of(piece, d, b) != DT_HIP_SUCCESS) return DT_HIP_INVALID_ARG;
   const size_t ncells = (size_t)b.size_x * b.size_y * b.size_z;
-  float *buf = (float *)dt_hip_alloc_device_buffer(devid, ncells * sizeof(float));
-  if(!buf) return DT_HIP_SYSMEM_ALLOCATION;
+  const dev_buf_t grid = dev_buf_t::alloc(devid, ncells * sizeof(float));
+  if(!grid) return DT_HIP_SYSMEM_ALLOCATION;
+  float *const buf = grid.as<float>();
   int err = bilat_splat_rows(devid, b, buf, (const float4 *)dev_in, 0, height, 0, (const float2 *)cells);
   if(err == DT_HIP_SUCCESS) err = bilat_blur_and_slice(devid, b, buf, d, (const float4 *)dev_in, (float4 *)dev_out, 0, height);
-  dt_hip_release_mem_object(buf);
   return err;
 }
 int bilat_process_chain(int devid, const dt_hip_piece_t *piece, const dt_hip_bilat_data_t *d, dt_hip_mem_t dev_in, dt_hip_mem_t dev_out,
@@ -625,12 +626,13 @@ int bilat_process_chain(int devid, const dt_hip_piece_t *piece, const dt_hip_bil
   grid_t b;
   if(bilat_grid_of(piece, d, b) != DT_HIP_SUCCESS) return DT_HIP_INVALID_ARG;
   const size_t cells = (size_t)b.size_x * b.size_y * b.size_z;
-  float *buf = (float *)dt_hip_alloc_device_buffer(devid, cells * sizeof(float));
-  if(!buf) return DT_HIP_SYSMEM_ALLOCATION;
+  const dev_buf_t grid = dev_buf_t::alloc(devid, cells * sizeof(float));
+  if(!grid) return DT_HIP_SYSMEM_ALLOCATION;
+  float *const buf = grid.as<float>();
   int err = bilat_splat_rows(devid, b, buf, (const float4 *)dev_in, 0, height, 0, (const float2 *)pixel_cells);
   const float *blurred = nullptr;
-  float *second = nullptr;
-  if(err == DT_HIP_SUCCESS) err = bilat_blur(devid, b, buf, &blurred, &second);
+  dev_buf_t second;
+  if(err == DT_HIP_SUCCESS) err = bilat_blur(devid, b, buf, &blurred, second);
   if(err == DT_HIP_SUCCESS)
   {
     bilat_slice_args sl;
@@ -639,8 +641,6 @@ int bilat_process_chain(int devid, const dt_hip_piece_t *piece, const dt_hip_bil
     sl.norm = -d->detail * b.sigma_r * 0.04f;
     err = rgb_group_launch(devid, *chain, dev_in, dev_out, &sl);
   }
-  if(second) dt_hip_release_mem_object(second); // stream-ordered
-  dt_hip_release_mem_object(buf);
   return err;
 }
 } // namespace ansel
@@ -674,11 +674,11 @@ int dt_hip_iop_bilat_process(int devid, const dt_hip_piece_t *piece, const dt_hi
   const int gerr = bilat_grid_of(piece, d, b);
   if(gerr != DT_HIP_SUCCESS) return gerr;
   const size_t cells = (size_t)b.size_x * b.size_y * b.size_z;
-  float *buf = (float *)dt_hip_alloc_device_buffer(devid, cells * sizeof(float));
-  if(!buf) return DT_HIP_SYSMEM_ALLOCATION;
+  const dev_buf_t grid = dev_buf_t::alloc(devid, cells * sizeof(float));
+  if(!grid) return DT_HIP_SYSMEM_ALLOCATION;
+  float *const buf = grid.as<float>();
   int err = bilat_splat_rows(devid, b, buf, (const float4 *)dev_in, 0, height, 0);
   if(err == DT_HIP_SUCCESS) err = bilat_blur_and_slice(devid, b, buf, d, (const float4 *)dev_in, (float4 *)dev_out, 0, height);
-  dt_hip_release_mem_object(buf);
   return err;
 }
 

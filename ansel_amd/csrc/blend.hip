@@ -966,7 +966,7 @@ extern "C" int dt_hip_develop_blend_process(int devid, const dt_hip_piece_t *pie
   // drawn / raster masks and the details threshold: rendered and refined by the host into ONE plane, as the reference's
   // device blend receives them (blend.c:1278-1325)
   const float *form = (const float *)d->form_mask;
-  float *refined = nullptr; // the form mask times the detail mask, built here when the raw detail mask is at hand
+  dev_buf_t refined; // the form mask times the detail mask, built here when the raw detail mask is at hand
   if((d->mask_mode & (DT_HIP_MASK_SHAPE | DT_HIP_MASK_RASTER)) && !form)
   {
     set_last_error("blend: a drawn / raster mask needs the host-rendered form mask (form_mask)");
@@ -1021,15 +1021,12 @@ extern "C" int dt_hip_develop_blend_process(int devid, const dt_hip_piece_t *pie
       set_last_error("blend: the details threshold in the raw colourspace is not built");
       return DT_HIP_INVALID_ARG;
     }
-    refined = (float *)dt_hip_alloc_device_buffer(devid, (size_t)a.owidth * a.oheight * sizeof(float));
+    refined = dev_buf_t::alloc(devid, (size_t)a.owidth * a.oheight * sizeof(float));
     if(!refined) return DT_HIP_SYSMEM_ALLOCATION;
-    const int rerr = detail_refine_launch(devid, (const float *)d->detail_mask, form, seed, d->details, a.owidth, a.oheight, refined);
-    if(rerr != DT_HIP_SUCCESS)
-    {
-      dt_hip_release_mem_object(refined);
-      return rerr;
-    }
-    form = refined;
+    const int rerr = detail_refine_launch(devid, (const float *)d->detail_mask, form, seed, d->details, a.owidth, a.oheight,
+                                          refined.as<float>());
+    if(rerr != DT_HIP_SUCCESS) return rerr;
+    form = refined.as<float>();
   }
   int form_kind = 0; // form_mask_kernel: 0 = no form plane involved
   if(raster_only)
@@ -1075,28 +1072,22 @@ extern "C" int dt_hip_develop_blend_process(int devid, const dt_hip_piece_t *pie
     // its input there
     set_last_error("blend: feathering guided by the module's input needs roi_in == roi_out (the reference reads outside "
                    "its input otherwise)");
-    if(refined) dt_hip_release_mem_object(refined);
     return DT_HIP_INVALID_ARG;
   }
   const bool spatial = blur || feather;
   const size_t np = (size_t)a.owidth * a.oheight;
   hipStream_t s = stream_of(devid);
   // the blurred mask plane: `plane` holds the mask, `scratch` / `scratch2` the causal and the anticausal half of a pass
-  float *plane = nullptr, *scratch = nullptr, *scratch2 = nullptr;
+  // (stream-ordered: what they give back is re-used only by later launches)
+  dev_buf_t plane_buf, scratch_buf, scratch2_buf;
   if(spatial || form_kind)
   {
-    plane = (float *)dt_hip_alloc_device_buffer(devid, np * sizeof(float));
-    if(blur) scratch = (float *)dt_hip_alloc_device_buffer(devid, np * sizeof(float));
-    if(blur) scratch2 = (float *)dt_hip_alloc_device_buffer(devid, np * sizeof(float));
-    if(!plane || (blur && (!scratch || !scratch2)))
-    {
-      if(plane) dt_hip_release_mem_object(plane);
-      if(scratch) dt_hip_release_mem_object(scratch);
-      if(scratch2) dt_hip_release_mem_object(scratch2);
-      if(refined) dt_hip_release_mem_object(refined);
-      return DT_HIP_SYSMEM_ALLOCATION;
-    }
+    plane_buf = dev_buf_t::alloc(devid, np * sizeof(float));
+    if(blur) scratch_buf = dev_buf_t::alloc(devid, np * sizeof(float));
+    if(blur) scratch2_buf = dev_buf_t::alloc(devid, np * sizeof(float));
+    if(!plane_buf || (blur && (!scratch_buf || !scratch2_buf))) return DT_HIP_SYSMEM_ALLOCATION;
   }
+  float *const plane = plane_buf.as<float>(), *const scratch = scratch_buf.as<float>(), *const scratch2 = scratch2_buf.as<float>();
   auto blur_plane = [&]() {
     // compute_gauss_params(), gaussian.c:44-95, order 0; sigma = blur_radius * roi_out->scale (blend.c:871)
     gauss_args g;
@@ -1139,12 +1130,6 @@ extern "C" int dt_hip_develop_blend_process(int devid, const dt_hip_piece_t *pie
       }
     }
   };
-  auto release_planes = [&]() {
-    if(plane) dt_hip_release_mem_object(plane);   // stream-ordered: re-used only by later launches
-    if(scratch) dt_hip_release_mem_object(scratch);
-    if(scratch2) dt_hip_release_mem_object(scratch2);
-    if(refined) dt_hip_release_mem_object(refined);
-  };
   if(raw)
   {
     // dt_develop_blendif_raw_make_mask(), blendif_raw.c:36-62: global opacity, optionally inverted -- the
@@ -1161,7 +1146,6 @@ extern "C" int dt_hip_develop_blend_process(int devid, const dt_hip_piece_t *pie
       launch_scope ls(devid, "blend_raw");
       blend_raw_kernel<<<pixel_grid(np), 256, 0, s>>>((const float *)dev_in, (float *)dev_out, plane, a);
     }
-    release_planes();
     return check_launch("blend_raw");
   }
   if(per_pixel)
@@ -1229,11 +1213,7 @@ extern "C" int dt_hip_develop_blend_process(int devid, const dt_hip_piece_t *pie
   else if(!per_pixel && a.tone)
     a.constant = tone_curve(a.constant, a); // the same value for every pixel
   if(spatial) spatial_ops();
-  if(post_err != DT_HIP_SUCCESS)
-  {
-    release_planes();
-    return post_err;
-  }
+  if(post_err != DT_HIP_SUCCESS) return post_err;
   {
     launch_scope ls(devid, "blend_kernel");
 #define BLEND_LAUNCH(CS_)                                                                   \
@@ -1248,6 +1228,5 @@ extern "C" int dt_hip_develop_blend_process(int devid, const dt_hip_piece_t *pie
     else BLEND_LAUNCH(DT_HIP_BLEND_CS_RGB_SCENE);
 #undef BLEND_LAUNCH
   }
-  release_planes();
   return check_launch("blend_kernel");
 }

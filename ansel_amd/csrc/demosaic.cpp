@@ -90,14 +90,14 @@ int dt_hip_iop_demosaic_process_band(int devid, const dt_hip_piece_t *piece, con
   // dt_dev_get_roi_filters(), src/develop/imageop.c:139-142
   const uint32_t filters = dt_hip_crop_dcraw_filters(piece->filters, piece->roi_in.x, piece->roi_in.y);
   const float *in = (const float *)dev_in;
-  float *geq = nullptr, *med = nullptr;
+  dev_buf_t geq_buf, aux_buf, med_buf;
   int err = DT_HIP_SUCCESS;
-  float *aux = nullptr;
   if(d->green_eq && !pass) // (the passthrough modes take the mosaic as it came in, demosaic.c:1111-1118)
   {
     // demosaic.c:1137-1163: _FULL = favg, _LOCAL = lavg, _BOTH = favg then lavg
-    geq = (float *)dt_hip_alloc_device_buffer(devid, (size_t)w * h * sizeof(float));
-    if(d->green_eq == 3) aux = (float *)dt_hip_alloc_device_buffer(devid, (size_t)w * h * sizeof(float));
+    geq_buf = dev_buf_t::alloc(devid, (size_t)w * h * sizeof(float));
+    if(d->green_eq == 3) aux_buf = dev_buf_t::alloc(devid, (size_t)w * h * sizeof(float));
+    float *const geq = geq_buf.as<float>(), *const aux = aux_buf.as<float>();
     if(!geq || (d->green_eq == 3 && !aux)) err = DT_HIP_SYSMEM_ALLOCATION;
     if(err == DT_HIP_SUCCESS && d->green_eq >= 2)
       err = green_eq_favg_launch(devid, in, aux ? aux : geq, w, h, piece->filters, piece->roi_in.x, piece->roi_in.y);
@@ -129,10 +129,11 @@ int dt_hip_iop_demosaic_process_band(int devid, const dt_hip_piece_t *piece, con
         }
         if(d->median_thrs > 0.0f)
         {
-          med = (float *)dt_hip_alloc_device_buffer(devid, (size_t)w * h * sizeof(float));
-          err = med ? pre_median_launch(devid, in, med, w, h, filters, d->median_thrs) : DT_HIP_SYSMEM_ALLOCATION;
+          med_buf = dev_buf_t::alloc(devid, (size_t)w * h * sizeof(float));
+          err = med_buf ? pre_median_launch(devid, in, med_buf.as<float>(), w, h, filters, d->median_thrs) : DT_HIP_SYSMEM_ALLOCATION;
         }
-        if(err == DT_HIP_SUCCESS) err = ppg_demosaic_launch(devid, piece, filters, med ? med : in, in, (float4 *)dev_out);
+        if(err == DT_HIP_SUCCESS)
+          err = ppg_demosaic_launch(devid, piece, filters, med_buf ? med_buf.as<float>() : in, in, (float4 *)dev_out);
         break;
       case DT_HIP_DEMOSAIC_AMAZE:
         err = amaze_demosaic_launch(devid, piece, filters, in, (float4 *)dev_out, band);
@@ -146,9 +147,6 @@ int dt_hip_iop_demosaic_process_band(int devid, const dt_hip_piece_t *piece, con
     err = dual_demosaic_launch(devid, piece, (const float *)dev_in, (float4 *)dev_out, d->dual_thrs, d->wb_coeffs);
   if(err == DT_HIP_SUCCESS && d->color_smoothing)
     err = color_smoothing_launch(devid, (float4 *)dev_out, piece->roi_out.width, piece->roi_out.height, (int)d->color_smoothing);
-  if(geq) dt_hip_release_mem_object(geq);
-  if(aux) dt_hip_release_mem_object(aux);
-  if(med) dt_hip_release_mem_object(med);
   return err;
 }
 

@@ -1034,8 +1034,10 @@ int amaze_demosaic_launch(int devid, const dt_hip_piece_t *piece, uint32_t filte
   {
     const int blocks = a.ntiles < sb_max ? a.ntiles : sb_max;
     // a slab per workgroup: any of them may draw a tile of the first kind
-    float *slabs = (float *)dt_hip_alloc_device_buffer(devid, (size_t)blocks * O_END * sizeof(float));
-    unsigned int *queue = (unsigned int *)dt_hip_alloc_device_buffer(devid, 256);
+    const dev_buf_t slabs_buf = dev_buf_t::alloc(devid, (size_t)blocks * O_END * sizeof(float));
+    const dev_buf_t queue_buf = dev_buf_t::alloc(devid, 256);
+    float *const slabs = slabs_buf.as<float>();
+    unsigned int *const queue = queue_buf.as<unsigned int>();
     int rc = DT_HIP_SUCCESS;
     if(!slabs || !queue)
       rc = DT_HIP_SYSMEM_ALLOCATION;
@@ -1047,8 +1049,6 @@ int amaze_demosaic_launch(int devid, const dt_hip_piece_t *piece, uint32_t filte
       amaze_frame<<<blocks, amz::STREAM_THREADS, amz::LDS_BYTES, s>>>(in, (float *)out, slabs, a, sa, queue);
     }
     if(rc == DT_HIP_SUCCESS) rc = check_launch("amaze_frame");
-    if(queue) dt_hip_release_mem_object(queue);
-    if(slabs) dt_hip_release_mem_object(slabs);
     return rc;
   }
   if(stream_tiles > 0)
@@ -1058,8 +1058,9 @@ int amaze_demosaic_launch(int devid, const dt_hip_piece_t *piece, uint32_t filte
     // the phase-clock instantiation exists in the measuring library only (tools/amaze_stage_clocks.py)
     if(timed)
     {
-      unsigned long long *stamps = (unsigned long long *)dt_hip_alloc_device_buffer(devid, sizeof(unsigned long long) * 32);
-      if(!stamps) return DT_HIP_SYSMEM_ALLOCATION;
+      const dev_buf_t stamps_buf = dev_buf_t::alloc(devid, sizeof(unsigned long long) * 32);
+      if(!stamps_buf) return DT_HIP_SYSMEM_ALLOCATION;
+      unsigned long long *const stamps = stamps_buf.as<unsigned long long>();
       unsigned long long host[32];
       if(hipMemsetAsync(stamps, 0, sizeof(host), s) == hipSuccess)
       {
@@ -1068,7 +1069,6 @@ int amaze_demosaic_launch(int devid, const dt_hip_piece_t *piece, uint32_t filte
           for(int k = 0; k < 16; k++)
             fprintf(stderr, "[amaze_stream_timed] phase %d cycles_per_tile %llu\n", k, host[k] / (unsigned long long)stream_tiles);
       }
-      dt_hip_release_mem_object(stamps);
     }
     else
 #endif
@@ -1084,17 +1084,15 @@ int amaze_demosaic_launch(int devid, const dt_hip_piece_t *piece, uint32_t filte
   const char *const blocks_env = measuring_env("ANSEL_HIP_AMAZE_BLOCKS");
   const int max_blocks = ov_blocks > 0 ? ov_blocks : (blocks_env ? atoi(blocks_env) : 512);
   const int blocks = a.ntiles < max_blocks ? a.ntiles : max_blocks;
-  float *slabs = (float *)dt_hip_alloc_device_buffer(devid, (size_t)blocks * O_END * sizeof(float));
-  if(!slabs) return DT_HIP_SYSMEM_ALLOCATION;
+  const dev_buf_t slabs_buf = dev_buf_t::alloc(devid, (size_t)blocks * O_END * sizeof(float));
+  if(!slabs_buf) return DT_HIP_SYSMEM_ALLOCATION;
+  float *const slabs = slabs_buf.as<float>();
   if(timed)
   {
     // the measuring build: cycles per stage summed over the tiles, printed (tools/amaze_stage_clocks.py)
-    unsigned long long *stamps = (unsigned long long *)dt_hip_alloc_device_buffer(devid, sizeof(unsigned long long) * N_STAMPS);
-    if(!stamps)
-    {
-      dt_hip_release_mem_object(slabs);
-      return DT_HIP_SYSMEM_ALLOCATION;
-    }
+    const dev_buf_t stamps_buf = dev_buf_t::alloc(devid, sizeof(unsigned long long) * N_STAMPS);
+    if(!stamps_buf) return DT_HIP_SYSMEM_ALLOCATION;
+    unsigned long long *const stamps = stamps_buf.as<unsigned long long>();
     unsigned long long host[N_STAMPS];
     if(hipMemsetAsync(stamps, 0, sizeof(host), s) == hipSuccess)
     {
@@ -1102,14 +1100,12 @@ int amaze_demosaic_launch(int devid, const dt_hip_piece_t *piece, uint32_t filte
       if(hipMemcpyAsync(host, stamps, sizeof(host), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess)
         for(int k = 0; k < 14; k++) fprintf(stderr, "[amaze_timed] stamp %d cycles_per_tile %llu\n", k, host[k] / (unsigned long long)(slab_tiles > 0 ? slab_tiles : 1));
     }
-    dt_hip_release_mem_object(stamps);
   }
   else
   {
     launch_scope ls(devid, "amaze_tiles");
     amaze_tiles<false><<<blocks, SLAB_THREADS, 0, s>>>(in, (float *)out, slabs, a, nullptr);
   }
-  dt_hip_release_mem_object(slabs);
   return check_launch("amaze_tiles");
 }
 

@@ -251,8 +251,9 @@ int green_eq_favg_launch(int devid, const float *in, float *out, int width, int 
   const int oi = (FCh(y, x) & 1) != 1 ? 1 : 0;
   const int g2_offset = oi ? -1 : 1;
   hipStream_t s = stream_of(devid);
-  dd_t *partial = (dd_t *)dt_hip_alloc_device_buffer(devid, sizeof(dd_t) * 2 * FAVG_BLOCKS + 2 * sizeof(double));
-  if(!partial) return DT_HIP_SYSMEM_ALLOCATION;
+  const dev_buf_t sums = dev_buf_t::alloc(devid, sizeof(dd_t) * 2 * FAVG_BLOCKS + 2 * sizeof(double));
+  if(!sums) return DT_HIP_SYSMEM_ALLOCATION;
+  dd_t *const partial = sums.as<dd_t>();
   double *ratio = (double *)(partial + 2 * FAVG_BLOCKS);
   {
     launch_scope ls(devid, "green_eq_favg_sums");
@@ -263,7 +264,6 @@ int green_eq_favg_launch(int devid, const float *in, float *out, int width, int 
     launch_scope ls(devid, "green_eq_favg_apply");
     green_eq_favg_apply<<<dim3((width + 63) / 64, (height + 3) / 4), 256, 0, s>>>(in, out, width, height, oi, g2_offset, ratio);
   }
-  dt_hip_release_mem_object(partial);
   return check_launch("green_eq_favg");
 }
 

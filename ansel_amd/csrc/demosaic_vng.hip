@@ -260,8 +260,10 @@ int vng4_demosaic_launch(int devid, const dt_hip_piece_t *piece, const float *in
   const uint32_t filters4 = filters4_of(piece->filters);
   vng_code host_codes[16];
   build_codes(filters4, host_codes);
-  vng_code *codes = (vng_code *)dt_hip_alloc_device_buffer(devid, sizeof(host_codes));
-  float4 *lin = (float4 *)dt_hip_alloc_device_buffer(devid, (size_t)w * h * sizeof(float4));
+  const dev_buf_t codes_buf = dev_buf_t::alloc(devid, sizeof(host_codes));
+  const dev_buf_t lin_buf = dev_buf_t::alloc(devid, (size_t)w * h * sizeof(float4));
+  vng_code *const codes = codes_buf.as<vng_code>();
+  float4 *const lin = lin_buf.as<float4>();
   int err = (codes && lin) ? DT_HIP_SUCCESS : DT_HIP_SYSMEM_ALLOCATION;
   hipStream_t s = stream_of(devid);
   if(err == DT_HIP_SUCCESS
@@ -280,8 +282,6 @@ int vng4_demosaic_launch(int devid, const dt_hip_piece_t *piece, const float *in
     }
     err = check_launch("vng4");
   }
-  if(codes) dt_hip_release_mem_object(codes);
-  if(lin) dt_hip_release_mem_object(lin);
   return err;
 }
 
@@ -295,8 +295,10 @@ int dual_demosaic_launch(int devid, const dt_hip_piece_t *piece, const float *ra
   if(!(dual_threshold > 0.0f)) return DT_HIP_SUCCESS; // :50 (`dual_threshold <= 0.0f`; a NaN threshold blends in the reference:
                                                       // not a state commit_params() leaves, refused by the caller)
   const size_t n = (size_t)w * h;
-  float4 *vng = (float4 *)dt_hip_alloc_device_buffer(devid, n * sizeof(float4));
-  float *mask = (float *)dt_hip_alloc_device_buffer(devid, n * sizeof(float));
+  const dev_buf_t vng_buf = dev_buf_t::alloc(devid, n * sizeof(float4));
+  const dev_buf_t mask_buf = dev_buf_t::alloc(devid, n * sizeof(float));
+  float4 *const vng = vng_buf.as<float4>();
+  float *const mask = mask_buf.as<float>();
   int err = (vng && mask) ? DT_HIP_SUCCESS : DT_HIP_SYSMEM_ALLOCATION;
   if(err == DT_HIP_SUCCESS) err = vng4_demosaic_launch(devid, piece, raw, vng);
   if(err == DT_HIP_SUCCESS) err = color_smoothing_launch(devid, vng, w, h, 2);
@@ -308,8 +310,6 @@ int dual_demosaic_launch(int devid, const dt_hip_piece_t *piece, const float *ra
     dual_blend<<<pixel_grid(n), 256, 0, stream_of(devid)>>>(rgb, vng, mask, n);
     err = check_launch("dual_blend");
   }
-  if(vng) dt_hip_release_mem_object(vng);
-  if(mask) dt_hip_release_mem_object(mask);
   return err;
 }
 

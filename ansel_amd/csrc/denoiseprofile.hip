@@ -33,6 +33,7 @@
 #include "nlmeans_core_params.h"
 
 #include <math.h>
+#include <utility>
 
 using namespace ansel;
 
@@ -1163,8 +1164,9 @@ int denoise_nlmeans(int devid, const dt_hip_piece_t *piece, const dt_hip_denoise
   const size_t npix_out = (size_t)w * (band ? band->row1 - band->row0 : h);
   dn_setup s;
   setup(piece, d, s, true);
-  float4 *pre = (float4 *)dt_hip_alloc_device_buffer(devid, npix_in * sizeof(float4));
-  if(!pre) return DT_HIP_SYSMEM_ALLOCATION;
+  dev_buf_t pre_buf = dev_buf_t::alloc(devid, npix_in * sizeof(float4));
+  if(!pre_buf) return DT_HIP_SYSMEM_ALLOCATION;
+  float4 *const pre = pre_buf.as<float4>();
   hipStream_t st = stream_of(devid);
   {
     vst_args fa;
@@ -1175,7 +1177,7 @@ int denoise_nlmeans(int devid, const dt_hip_piece_t *piece, const dt_hip_denoise
   nlm_core_params_t p = nlm_params_of(piece, d);
   p.band = band;
   int err = nlmeans_core_launch(devid, pre, (float4 *)dev_out, w, h, p);
-  dt_hip_release_mem_object(pre);
+  pre_buf.release(); // stream-ordered
   if(err != DT_HIP_SUCCESS) return err;
   {
     vst_args ia;
@@ -1223,26 +1225,19 @@ struct dn_band_job_t
   int devid, w, frame_h, max_scale, row0, rows;
   dt_hip_denoiseprofile_data_t d;
   dn_setup s;
-  float4 *cur;          // coarse plane of scale next_scale - 1: [cur_top][rows][cur_bottom] rows
+  dev_buf_t cur;        // coarse plane of scale next_scale - 1: [cur_top][rows][cur_bottom] rows of float4
   int cur_top, cur_bottom;
-  float4 *det[BANDS];   // own rows
-  double *sums;         // [max_scale][frame_h * nseg][4]
-  double *local;        // own rows' partial sums of one scale
-  float *thrs;
+  dev_buf_t det[BANDS]; // own rows (float4)
+  dev_buf_t sums;       // double [max_scale][frame_h * nseg][4]
+  dev_buf_t local;      // own rows' partial sums of one scale (double)
+  dev_buf_t thrs;       // float [BANDS][4]
   int next_scale;
   bool sums_requested;
 };
 
 void denoiseprofile_band_abort(dn_band_job_t *j)
 {
-  if(!j) return;
-  if(j->cur) dt_hip_release_mem_object(j->cur);
-  for(int k = 0; k < BANDS; k++)
-    if(j->det[k]) dt_hip_release_mem_object(j->det[k]);
-  if(j->sums) dt_hip_release_mem_object(j->sums);
-  if(j->local) dt_hip_release_mem_object(j->local);
-  if(j->thrs) dt_hip_release_mem_object(j->thrs);
-  delete j;
+  delete j; // its planes go back to the pool with it
 }
 
 // rows of the module INPUT a band needs from each neighbour; the wavelets then ask for 2 * 2^k rows of their own
@@ -1267,8 +1262,7 @@ int denoiseprofile_band_begin(int devid, const dt_hip_piece_t *piece, const dt_h
   if(piece->channels != 4 || !(piece->roi_in.scale > 0.0)) return DT_HIP_INVALID_ARG;
   if(DT_HIP_DENOISEPROFILE_IS_NLMEANS(d->mode)) return denoise_nlmeans(devid, piece, d, band, buf_rows, dev_in, dev_out);
   if(!DT_HIP_DENOISEPROFILE_IS_WAVELETS(d->mode)) return DT_HIP_INVALID_ARG;
-  dn_band_job_t *j = new dn_band_job_t;
-  memset(j, 0, sizeof(*j));
+  dn_band_job_t *j = new dn_band_job_t();
   j->devid = devid;
   j->w = piece->roi_in.width;
   j->frame_h = band->frame_h;
@@ -1288,17 +1282,17 @@ int denoiseprofile_band_begin(int devid, const dt_hip_piece_t *piece, const dt_h
   const size_t sums_bytes = (size_t)j->max_scale * n_frame * 4 * sizeof(double);
   j->cur_top = band->row0 - band->buf_row0;
   j->cur_bottom = buf_rows - j->cur_top - j->rows;
-  bool ok = (j->cur = (float4 *)dt_hip_alloc_device_buffer(devid, npix * sizeof(float4))) != nullptr;
-  ok &= (j->sums = (double *)dt_hip_alloc_device_buffer(devid, sums_bytes)) != nullptr;
-  ok &= (j->local = (double *)dt_hip_alloc_device_buffer(devid, (size_t)j->rows * nseg * 4 * sizeof(double))) != nullptr;
-  ok &= (j->thrs = (float *)dt_hip_alloc_device_buffer(devid, BANDS * 4 * sizeof(float))) != nullptr;
+  bool ok = (bool)(j->cur = dev_buf_t::alloc(devid, npix * sizeof(float4)));
+  ok &= (bool)(j->sums = dev_buf_t::alloc(devid, sums_bytes));
+  ok &= (bool)(j->local = dev_buf_t::alloc(devid, (size_t)j->rows * nseg * 4 * sizeof(double)));
+  ok &= (bool)(j->thrs = dev_buf_t::alloc(devid, BANDS * 4 * sizeof(float)));
   if(!ok || j->cur_bottom < 0)
   {
     denoiseprofile_band_abort(j);
     return DT_HIP_SYSMEM_ALLOCATION;
   }
   hipStream_t st = stream_of(devid);
-  if(hipMemsetAsync(j->sums, 0, sums_bytes, st) != hipSuccess)
+  if(hipMemsetAsync(j->sums.ptr(), 0, sums_bytes, st) != hipSuccess)
   {
     denoiseprofile_band_abort(j);
     return DT_HIP_DEFAULT_ERROR;
@@ -1308,7 +1302,7 @@ int denoiseprofile_band_begin(int devid, const dt_hip_piece_t *piece, const dt_h
     vst_args fa;
     forward_args(j->s, fa);
     launch_scope ls(devid, "dn_precondition");
-    dn_precondition<<<pixel_grid(npix), 256, 0, st>>>((const float4 *)dev_in, j->cur, npix, fa);
+    dn_precondition<<<pixel_grid(npix), 256, 0, st>>>((const float4 *)dev_in, j->cur.as<float4>(), npix, fa);
   }
   const int err = check_launch("dn_precondition");
   if(err != DT_HIP_SUCCESS)
@@ -1335,7 +1329,7 @@ int denoiseprofile_band_step(dn_band_job_t *j, dt_hip_mem_t *halo_buf, int *halo
   {
     if(j->sums_requested) return 0;
     j->sums_requested = true;
-    *sums = j->sums;
+    *sums = j->sums.as<double>();
     *sum_count = (size_t)j->max_scale * n_frame * 4;
     return 2;
   }
@@ -1345,11 +1339,10 @@ int denoiseprofile_band_step(dn_band_job_t *j, dt_hip_mem_t *halo_buf, int *halo
   // the coarse plane of this scale, with room for the rows the next scale reads beyond the band
   const int h_next = last ? 0 : 2 * (2 << scale);
   const int top = clip_halo(h_next, j->row0), bottom = clip_halo(h_next, j->frame_h - j->row0 - j->rows);
-  float4 *coarse = (float4 *)dt_hip_alloc_device_buffer(devid, (size_t)(top + j->rows + bottom) * w * sizeof(float4));
-  j->det[scale] = (float4 *)dt_hip_alloc_device_buffer(devid, (size_t)j->rows * w * sizeof(float4));
+  dev_buf_t coarse = dev_buf_t::alloc(devid, (size_t)(top + j->rows + bottom) * w * sizeof(float4));
+  j->det[scale] = dev_buf_t::alloc(devid, (size_t)j->rows * w * sizeof(float4));
   if(!coarse || !j->det[scale])
   {
-    if(coarse) dt_hip_release_mem_object(coarse);
     denoiseprofile_band_abort(j);
     return DT_HIP_SYSMEM_ALLOCATION;
   }
@@ -1357,17 +1350,16 @@ int denoiseprofile_band_step(dn_band_job_t *j, dt_hip_mem_t *halo_buf, int *halo
   const float sigma_band = powf(varf, scale) * 1.0f;
   {
     launch_scope ls(devid, "dn_decompose");
-    launch_decompose(st, j->cur, coarse + (size_t)top * w, j->det[scale], j->local, w, j->rows, mult,
+    launch_decompose(st, j->cur.as<float4>(), coarse.as<float4>() + (size_t)top * w, j->det[scale].as<float4>(), j->local.as<double>(), w, j->rows, mult,
                      1.0f / (sigma_band * sigma_band), nseg, j->cur_top, j->cur_top + j->rows + j->cur_bottom);
   }
   int err = check_launch("denoiseprofile band decompose");
   // the own rows' partial sums at their place in the frame's table
   if(err == DT_HIP_SUCCESS
-     && hipMemcpyAsync(j->sums + ((size_t)scale * n_frame + (size_t)j->row0 * nseg) * 4, j->local,
+     && hipMemcpyAsync(j->sums.as<double>() + ((size_t)scale * n_frame + (size_t)j->row0 * nseg) * 4, j->local.ptr(),
                        (size_t)j->rows * nseg * 4 * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
     err = DT_HIP_DEFAULT_ERROR;
-  dt_hip_release_mem_object(j->cur); // stream-ordered
-  j->cur = coarse;
+  j->cur = std::move(coarse); // the plane it held goes back to the pool (stream-ordered)
   j->cur_top = top;
   j->cur_bottom = bottom;
   j->next_scale++;
@@ -1378,7 +1370,7 @@ int denoiseprofile_band_step(dn_band_job_t *j, dt_hip_mem_t *halo_buf, int *halo
   }
   if(!last && (top || bottom))
   {
-    *halo_buf = coarse;
+    *halo_buf = j->cur.ptr();
     *halo_rows = h_next;
     return 1;
   }
@@ -1397,8 +1389,9 @@ int denoiseprofile_band_finish(dn_band_job_t *j, dt_hip_mem_t dev_out)
   synth_args sy;
   memset(&sy, 0, sizeof(sy));
   sy.nbands = j->max_scale;
-  sy.thrs = j->thrs;
-  double *accs = (double *)dt_hip_alloc_device_buffer(devid, (size_t)BANDS * 4 * 1024 * sizeof(double));
+  sy.thrs = j->thrs.as<float>();
+  const dev_buf_t accs_buf = dev_buf_t::alloc(devid, (size_t)BANDS * 4 * 1024 * sizeof(double));
+  double *const accs = accs_buf.as<double>();
   if(!accs) err = DT_HIP_SYSMEM_ALLOCATION;
   thr_args_all all;
   memset(&all, 0, sizeof(all));
@@ -1406,13 +1399,13 @@ int denoiseprofile_band_finish(dn_band_job_t *j, dt_hip_mem_t dev_out)
   {
     all.band[scale].n_partial = n_frame;
     threshold_args(&j->d, scale, j->max_scale, (size_t)j->w * j->frame_h, all.band[scale]);
-    sy.detail[scale] = j->det[scale];
+    sy.detail[scale] = j->det[scale].as<float4>();
   }
   if(err == DT_HIP_SUCCESS)
   {
     launch_scope ls(devid, "dn_band_threshold");
-    dn_band_sums<<<dim3(THR_GROUPS, j->max_scale), 64, 0, st>>>(j->sums, n_frame, accs);
-    dn_band_threshold<<<j->max_scale, 1024, 0, st>>>(accs, all, j->thrs);
+    dn_band_sums<<<dim3(THR_GROUPS, j->max_scale), 64, 0, st>>>(j->sums.as<double>(), n_frame, accs);
+    dn_band_threshold<<<j->max_scale, 1024, 0, st>>>(accs, all, j->thrs.as<float>());
     err = check_launch("denoiseprofile band threshold");
   }
   if(err == DT_HIP_SUCCESS)
@@ -1422,10 +1415,9 @@ int denoiseprofile_band_finish(dn_band_job_t *j, dt_hip_mem_t dev_out)
     vst_args ia;
     inverse_args(j->s, ia);
     launch_scope ls(devid, "dn_finish");
-    dn_finish<<<pixel_grid(npix), 256, 0, st>>>(out, j->cur + (size_t)j->cur_top * j->w, npix, ia, sy);
+    dn_finish<<<pixel_grid(npix), 256, 0, st>>>(out, j->cur.as<float4>() + (size_t)j->cur_top * j->w, npix, ia, sy);
     err = check_launch("dn_finish");
   }
-  if(accs) dt_hip_release_mem_object(accs);
   denoiseprofile_band_abort(j);
   return err;
 }
@@ -1468,9 +1460,11 @@ static int denoiseprofile_run(int devid, const dt_hip_piece_t *piece, const dt_h
   const size_t n_partial = (size_t)h * nseg;
   // the tables of partial sums of ALL bands: the thresholds are needed by dn_finish only, so they are reduced together
   // behind the last decomposition (seven pairs of latency-bound launches in a row cost 0.39 ms per frame)
-  double *partial = (double *)dt_hip_alloc_device_buffer(devid, (size_t)BANDS * n_partial * 4 * sizeof(double));
-  float *thrs = (float *)dt_hip_alloc_device_buffer(devid, BANDS * 4 * sizeof(float));
-  double *accs = (double *)dt_hip_alloc_device_buffer(devid, (size_t)BANDS * 4 * 1024 * sizeof(double));
+  const dev_buf_t partial_buf = dev_buf_t::alloc(devid, (size_t)BANDS * n_partial * 4 * sizeof(double));
+  const dev_buf_t thrs_buf = dev_buf_t::alloc(devid, BANDS * 4 * sizeof(float));
+  const dev_buf_t accs_buf = dev_buf_t::alloc(devid, (size_t)BANDS * 4 * 1024 * sizeof(double));
+  double *const partial = partial_buf.as<double>(), *const accs = accs_buf.as<double>();
+  float *const thrs = thrs_buf.as<float>();
   int err = (partial && thrs && accs) ? DT_HIP_SUCCESS : DT_HIP_SYSMEM_ALLOCATION;
   // Round 6: one COARSE plane per band, all alive until the single synthesis pass at the end, and ONE detail plane -- band 0's, whose
   // input (the transformed frame) is never stored.  The detail of every other band is the difference of two coarse planes and is formed
@@ -1479,12 +1473,14 @@ static int denoiseprofile_run(int devid, const dt_hip_piece_t *piece, const dt_h
   memset(&sy, 0, sizeof(sy));
   sy.nbands = s.max_scale;
   sy.thrs = thrs;
+  dev_buf_t coarse_buf[BANDS];
   float4 *coarse[BANDS] = { nullptr };
-  float4 *det0 = (float4 *)dt_hip_alloc_device_buffer(devid, plane);
+  const dev_buf_t det0_buf = dev_buf_t::alloc(devid, plane);
+  float4 *const det0 = det0_buf.as<float4>();
   if(!det0) err = DT_HIP_SYSMEM_ALLOCATION;
   for(int k = 0; k < s.max_scale && err == DT_HIP_SUCCESS; k++)
   {
-    coarse[k] = (float4 *)dt_hip_alloc_device_buffer(devid, plane);
+    coarse[k] = (coarse_buf[k] = dev_buf_t::alloc(devid, plane)).as<float4>();
     if(!coarse[k]) err = DT_HIP_SYSMEM_ALLOCATION;
     sy.detail[k] = k == 0 ? det0 : coarse[k];
   }
@@ -1495,10 +1491,11 @@ static int denoiseprofile_run(int devid, const dt_hip_piece_t *piece, const dt_h
   forward_args(s, fa);
   const float4 *b1 = (const float4 *)dev_in;
   // the Y0U0V0 transform sets the fourth channel to 0.0f: the decompositions leave it out for as long as it stays +0
+  dev_buf_t alpha_buf;
   unsigned *alpha_flag = nullptr;
   if(err == DT_HIP_SUCCESS && s.vst == 2)
   {
-    alpha_flag = (unsigned *)dt_hip_alloc_device_buffer(devid, sizeof(unsigned));
+    alpha_flag = (alpha_buf = dev_buf_t::alloc(devid, sizeof(unsigned))).as<unsigned>();
     if(!alpha_flag) err = DT_HIP_SYSMEM_ALLOCATION;
     else if(hipMemsetAsync(alpha_flag, 0, sizeof(unsigned), st) != hipSuccess) err = DT_HIP_DEFAULT_ERROR;
   }
@@ -1569,13 +1566,6 @@ static int denoiseprofile_run(int devid, const dt_hip_piece_t *piece, const dt_h
     }
     err = check_launch("dn_finish");
   }
-  if(det0) dt_hip_release_mem_object(det0);
-  for(int k = 0; k < BANDS; k++)
-    if(coarse[k]) dt_hip_release_mem_object(coarse[k]);
-  if(partial) dt_hip_release_mem_object(partial);
-  if(thrs) dt_hip_release_mem_object(thrs);
-  if(accs) dt_hip_release_mem_object(accs);
-  if(alpha_flag) dt_hip_release_mem_object(alpha_flag);
   return err;
 }
 

@@ -161,8 +161,9 @@ int detail_refine_launch(int devid, const float *rawdetail, const float *form, f
     return DT_HIP_INVALID_ARG;
   }
   const size_t n = (size_t)width * height;
-  float *tmp = (float *)dt_hip_alloc_device_buffer(devid, n * sizeof(float));
-  if(!tmp) return DT_HIP_SYSMEM_ALLOCATION;
+  const dev_buf_t tmp_buf = dev_buf_t::alloc(devid, n * sizeof(float));
+  if(!tmp_buf) return DT_HIP_SYSMEM_ALLOCATION;
+  float *const tmp = tmp_buf.as<float>();
   const int detail = level > 0.0f;
   // _detail_mask_threshold(), blend.c:355-359
   const float threshold = 0.005f * (detail ? powf(level, 2.0f) : 1.0f - powf(fabs(level), 0.5f));
@@ -177,7 +178,6 @@ int detail_refine_launch(int devid, const float *rawdetail, const float *form, f
     launch_scope ls(devid, "detail_refine");
     detail_refine<<<dim3((width + 63) / 64, (height + 3) / 4), 256, 0, s>>>(tmp, form, refined, width, height, fill, a);
   }
-  dt_hip_release_mem_object(tmp);
   return check_launch("detail_refine");
 }
 
@@ -187,14 +187,10 @@ int dual_blend_mask_launch(int devid, float4 *rgb, const float wb[3], float thre
 {
   if(width < 9 || height < 9) return DT_HIP_INVALID_ARG;
   const size_t n = (size_t)width * height;
-  float *lum = (float *)dt_hip_alloc_device_buffer(devid, n * sizeof(float));
-  float *raw = (float *)dt_hip_alloc_device_buffer(devid, n * sizeof(float));
-  if(!lum || !raw)
-  {
-    if(lum) dt_hip_release_mem_object(lum);
-    if(raw) dt_hip_release_mem_object(raw);
-    return DT_HIP_SYSMEM_ALLOCATION;
-  }
+  const dev_buf_t lum_buf = dev_buf_t::alloc(devid, n * sizeof(float));
+  const dev_buf_t raw_buf = dev_buf_t::alloc(devid, n * sizeof(float));
+  if(!lum_buf || !raw_buf) return DT_HIP_SYSMEM_ALLOCATION;
+  float *const lum = lum_buf.as<float>(), *const raw = raw_buf.as<float>();
   blur_args a;
   blur_9x9_coeff(a.c, 2.0f);
   hipStream_t s = stream_of(devid);
@@ -214,8 +210,6 @@ int dual_blend_mask_launch(int devid, float4 *rgb, const float wb[3], float thre
     launch_scope ls(devid, "detail_refine");
     detail_refine<<<dim3((width + 63) / 64, (height + 3) / 4), 256, 0, s>>>(lum, nullptr, mask, width, height, 1.0f, a);
   }
-  dt_hip_release_mem_object(lum);
-  dt_hip_release_mem_object(raw);
   return check_launch("dual_blend_mask");
 }
 
@@ -232,8 +226,9 @@ extern "C" int dt_hip_iop_detailmask_process(int devid, const dt_hip_piece_t *pi
     return DT_HIP_INVALID_ARG;
   }
   const size_t n = (size_t)width * height;
-  float *lum = (float *)dt_hip_alloc_device_buffer(devid, n * sizeof(float));
-  if(!lum) return DT_HIP_SYSMEM_ALLOCATION;
+  const dev_buf_t lum_buf = dev_buf_t::alloc(devid, n * sizeof(float));
+  if(!lum_buf) return DT_HIP_SYSMEM_ALLOCATION;
+  float *const lum = lum_buf.as<float>();
   hipStream_t s = stream_of(devid);
   {
     launch_scope ls(devid, "rawdetail_luminance");
@@ -243,6 +238,5 @@ extern "C" int dt_hip_iop_detailmask_process(int devid, const dt_hip_piece_t *pi
     launch_scope ls(devid, "rawdetail_scharr");
     rawdetail_scharr<<<dim3((width + 63) / 64, (height + 3) / 4), 256, 0, s>>>(lum, (float *)d->mask, width, height);
   }
-  dt_hip_release_mem_object(lum);
   return check_launch("detailmask");
 }

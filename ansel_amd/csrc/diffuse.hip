@@ -991,6 +991,243 @@ int diffuse_process_post_lab(int devid, const dt_hip_piece_t *piece, const dt_hi
   if(!lab || measuring_env("ANSEL_HIP_PDE_PER_ROW")) return DT_HIP_INVALID_ARG; // only the strip kernel has the tail
   return diffuse_run(devid, piece, d, 0, dev_in, dev_out, lab);
 }
+
+// The planes of one call (diffuse.c:1167-1195): HF[scales], two low-pass ping-pong, two iteration ping-pong (tmp[0] =
+// "temp2", tmp[1] = "temp1").
+// LF chain (every scale on the strip kernel): hf[s] holds the LOW-pass plane of scale s + 1 instead, nothing stores a
+// high-frequency plane, and one plane besides them, lf[0], serves the synthesis' ping-pong (a plane fewer than the
+// reference): while scale s is synthesised, hf[s + 1] has been read for the last time, so the running sum alternates between
+// lf[0] and hf[s + 1].  The chain reads the iteration's input until its last pass, so an iteration that writes the plane
+// it reads cannot take it: that iteration stores its high-frequency planes as the reference does, and needs lf[1].
+struct diffuse_planes_t
+{
+  dev_buf_t hf[DIFFUSE_MAX_SCALES], lf[2], tmp[2];
+  dev_buf_t mask;       // threshold > 0: the pixels above it ...
+  dev_buf_t inpainted;  // ... and the noise-seeded copy of the input (borrowed: it is tmp[1])
+  dev_buf_t alpha_flag; // the three-float sequence's gate
+};
+
+// what the parts of one call share
+struct diffuse_job_t
+{
+  int devid;
+  hipStream_t st;
+  const dt_hip_diffuse_data_t *d;
+  const dt_hip_lab_data_t *post_lab;
+  int w, h, scales, iterations;
+  float zoom;
+  bool lf_chain;
+  bool per_row, no_dma; // measuring builds: the per-row kernel / the rows through registers (round 4's fetch), for A/B timing
+  diffuse_planes_t p;
+};
+
+// in_place: the one iteration reads the plane it writes (dev_out == dev_in, no inpainted copy in between) -- with more
+// iterations than one, an iteration's input and output are always two planes.  three: the three-float sequence runs
+static int diffuse_alloc_planes(diffuse_job_t &j, const bool in_place, const bool three)
+{
+  diffuse_planes_t &p = j.p;
+  const size_t plane = (size_t)j.w * j.h * sizeof(float4);
+  bool ok = true;
+  for(int s = 0; s < j.scales; s++) ok &= (bool)(p.hf[s] = dev_buf_t::alloc(j.devid, plane));
+  for(int k = 0; k < ((j.lf_chain && !in_place) ? 1 : 2); k++) ok &= (bool)(p.lf[k] = dev_buf_t::alloc(j.devid, plane));
+  for(int k = 0; k < 2 && k < j.iterations - 1; k++) ok &= (bool)(p.tmp[k] = dev_buf_t::alloc(j.devid, plane));
+  if(ok && three) ok &= (bool)(p.alpha_flag = dev_buf_t::alloc(j.devid, sizeof(unsigned)));
+  if(ok && j.d->threshold > 0.0f)
+  {
+    // (the reference reuses "temp1" for the inpainted copy; the second iteration's output may overwrite it, so may ours)
+    p.mask = dev_buf_t::alloc(j.devid, (size_t)j.w * j.h);
+    if(!p.tmp[1]) p.tmp[1] = dev_buf_t::alloc(j.devid, plane);
+    p.inpainted = dev_buf_t::borrow(p.tmp[1].base());
+    ok = p.mask && p.inpainted;
+  }
+  return ok ? DT_HIP_SUCCESS : DT_HIP_SYSMEM_ALLOCATION;
+}
+
+// the fields of pde_args that hold for every launch of a call
+static void pde_args_of_call(pde_args &a, const int w, const int h, const dt_hip_diffuse_data_t *d)
+{
+  memset(&a, 0, sizeof(a));
+  a.width = w;
+  a.height = h;
+  a.wskip = measuring_env("ANSEL_HIP_PDE_NO_WSKIP") ? 0 : 1;
+  const char *const approx_env = measuring_env("ANSEL_HIP_PDE_APPROX_DIV"); // read per call: tools/pde_div_ab.py flips it
+  a.approx_div = approx_env && atoi(approx_env) != 0;
+  const char *const off_env = measuring_env("ANSEL_HIP_PDE_OFF"); // read per call: tools/pde_off_ab.py
+  a.off = off_env ? atoi(off_env) : 0;
+  const float user_aniso[4] = { d->anisotropy_first, d->anisotropy_second, d->anisotropy_third, d->anisotropy_fourth };
+  for(int k = 0; k < 4; k++)
+  {
+    a.anisotropy[k] = sqf(user_aniso[k]); // compute_anisotropy_factor(), diffuse.c:970-976
+    a.kind[k] = user_aniso[k] == 0.0f ? 0 : (user_aniso[k] > 0.0f ? 1 : 2);
+  }
+  a.same02 = a.kind[0] == a.kind[2] && a.anisotropy[0] == a.anisotropy[2];
+  a.same13 = a.kind[1] == a.kind[3] && a.anisotropy[1] == a.anisotropy[3];
+  a.variance_threshold = powf(10.0f, d->variance_threshold);
+}
+
+// ... and the per-band constants of scale s, diffuse.c:1053-1074.  last_pass: the pass that writes the module's output
+static void pde_args_of_scale(pde_args &a, const diffuse_job_t &j, const int s, const bool last_pass)
+{
+  const dt_hip_diffuse_data_t *const d = j.d;
+  const float regularization = powf(10.0f, d->regularization) - 1.0f; // diffuse.c:999-1000
+  const float speed[4] = { d->first, d->second, d->third, d->fourth };
+  const float real_radius = sigma_at_step(BSPLINE_SIGMA, (unsigned)s) * j.zoom;
+  a.regularization = regularization / 9.0f * sqf(real_radius);
+  const float norm = expf(-sqf(real_radius - (float)d->radius_center) / sqf((float)d->radius));
+  for(int k = 0; k < 4; k++) a.abcd[k] = speed[k] * PDE_KAPPA * norm;
+  a.strength = d->sharpness * norm + 1.0f;
+  a.mult = 1 << s;
+  a.post_lab = 0;
+  if(j.post_lab && last_pass)
+  {
+    a.post_lab = 1;
+    memcpy(a.post_m, j.post_lab->matrix, sizeof(a.post_m));
+  }
+}
+
+typedef void (*pde_strip_fn)(const float4 *, const float4 *, const float4 *, float4 *, pde_args, int, const unsigned char *, int, int);
+typedef void (*pde_strip3_fn)(const float4 *, const float4 *, const float4 *, float4 *, pde_args, int, int, int);
+
+// the strip kernel of a mode (-1: the kinds read at run time) in its three forms: the stored high-frequency planes, the
+// low-pass chain, the chain by LDS-DMA
+template <int MD> static pde_strip_fn pde_strip_forms(const bool chain, const bool dma)
+{
+  if(dma) return diffuse_pde_strip<true, MD, true>;
+  if(chain) return diffuse_pde_strip<true, MD>;
+  return diffuse_pde_strip<false, MD>;
+}
+static pde_strip_fn pde_strip_kernel(const int mode, const bool chain, const bool dma)
+{
+  switch(mode)
+  {
+#define PDE_CASE(MD) \
+  case MD: return pde_strip_forms<MD>(chain, dma);
+    PDE_MODES(PDE_CASE)
+#undef PDE_CASE
+    default: return pde_strip_forms<-1>(chain, dma);
+  }
+}
+// ... and on three-float planes.  h0_4: the first plane is the module's float4 input
+static pde_strip3_fn pde_strip3_kernel(const int mode, const bool h0_4)
+{
+  if(mode == PDE_MODE_DEBLUR) return h0_4 ? diffuse_pde_strip3<PDE_MODE_DEBLUR, true> : diffuse_pde_strip3<PDE_MODE_DEBLUR, false>;
+  return h0_4 ? diffuse_pde_strip3<PDE_MODE_ISOTROPIC, true> : diffuse_pde_strip3<PDE_MODE_ISOTROPIC, false>;
+}
+
+// One pass of the PDE on the strip kernel (a.mult <= PDE_SHARED_MULT): h0, h1 and cur are what the kernel reads (chain: the
+// low-pass planes of this scale and the next; otherwise the high-frequency plane and nothing), `to` what it writes.
+// p3: on three-float planes (then chain and dma hold)
+static void pde_strip_launch(const diffuse_job_t &j, const pde_args &a, const bool p3, const bool h0_4, const bool chain,
+                             const bool dma, const float4 *h0, const float4 *h1, const float4 *cur, float4 *to,
+                             const int final_pass)
+{
+  const int w = j.w, h = j.h;
+  const int classes = h < a.mult ? h : a.mult, per_class = (h + a.mult - 1) / a.mult;
+  const int gx = (w + 255) / 256;
+  int strip = 32;
+#ifdef ANSEL_HIP_MEASURING
+  static const char *const strip_env = measuring_env("ANSEL_HIP_PDE_STRIP"); // rows a workgroup keeps its columns for, for A/B timing
+  if(strip_env) strip = atoi(strip_env);
+#endif
+  while(strip > 4 && (size_t)gx * classes * ((per_class + strip - 1) / strip) < 2048) strip /= 2;
+  const int spc = (per_class + strip - 1) / strip;
+  size_t ring = (size_t)PDE_RING * (256 + 2 * a.mult) * sizeof(float4);
+#ifdef ANSEL_HIP_MEASURING
+  // how much the kernel needs its occupancy: LDS asked for and not used (bytes), for A/B timing
+  static const char *const pad_env = measuring_env("ANSEL_HIP_PDE_LDS_PAD");
+  if(pad_env) ring += (size_t)atoi(pad_env);
+#endif
+  static const bool generic = measuring_env("ANSEL_HIP_PDE_GENERIC") != nullptr; // the kinds read at run time, for A/B timing
+  const int mode = generic ? -1 : pde_mode_of(a);
+  const dim3 sgrid(gx, classes * spc);
+  if(p3)
+  {
+    // three-float planes: 12 B ring entries, and per wave a landing zone of 3 x 16 B slots (pde_dma_planes3())
+    const size_t lds3 = (size_t)PDE_RING * (256 + 2 * a.mult) * 12 + (size_t)4 * 3 * (64 + 2 * a.mult) * 16;
+    pde_strip3_kernel(mode, h0_4)<<<sgrid, 256, lds3, j.st>>>(h0, h1, cur, to, a, final_pass, strip, spc);
+    return;
+  }
+  // dma: the rows by LDS-DMA into per-wave landing zones behind the ring (the kernel's comment): the low-pass chain (three planes a row) at the dilations whose halo is at most a quarter of a wave
+  // (with a luminance mask the byte the row step loads makes the compiler wait for every vector-memory operation in flight,
+  // the row fetch included, in the middle of a step: masked runs keep the form -- same result -- but not its overlap)
+  const size_t lds = dma ? ring + (size_t)4 * 3 * (64 + 2 * a.mult) * sizeof(float4) : ring;
+  pde_strip_kernel(mode, chain, dma)<<<sgrid, 256, lds, j.st>>>(h0, h1, cur, to, a, final_pass, j.p.mask.as<unsigned char>(), strip, spc);
+}
+
+// One iteration, src -> dst: the analysis (scales fine to coarse), then the synthesis through the PDE (coarse to fine).
+// p3: on three-float planes (the first sequence of diffuse_run()); first / last: the module's first / last iteration.
+// The ping-pong of the running sum: the last pass (s == 0) writes dst; before it, the chain alternates between lf[0] and
+// hf[s + 1] (diffuse_planes_t), the stored-HF form between the two lf planes, beginning with the one that does not hold the
+// coarsest low-pass plane
+static int diffuse_iteration(const diffuse_job_t &j, pde_args &a, const bool p3, const bool first, const bool last,
+                             const float4 *src, float4 *dst)
+{
+  const int w = j.w, h = j.h, scales = j.scales;
+  float4 *hf[DIFFUSE_MAX_SCALES];
+  for(int s = 0; s < DIFFUSE_MAX_SCALES; s++) hf[s] = j.p.hf[s].as<float4>();
+  float4 *const lf[2] = { j.p.lf[0].as<float4>(), j.p.lf[1].as<float4>() };
+  unsigned *const alpha_flag = j.p.alpha_flag.as<unsigned>();
+  const unsigned char *const mask = j.p.mask.as<unsigned char>();
+  int err = DT_HIP_SUCCESS;
+  const float4 *level = src;
+  float4 *residual = lf[0];
+  // the chain reads the iteration's input until its last pass: not when that pass writes the same plane
+  const bool chain = j.lf_chain && (const float4 *)dst != src;
+  for(int s = 0; s < scales && err == DT_HIP_SUCCESS; s++)
+  {
+#ifdef ANSEL_HIP_MEASURING
+    // the chain keeps every low-pass plane: two scales in one pass where the pair kernel has the dilation (1 + 2, 4 + 8)
+    static const bool pairs = measuring_env("ANSEL_HIP_BSPLINE_PAIRS") != nullptr;
+    if(chain && pairs && s + 1 < scales && (s == 0 || s == 2))
+    {
+      err = bspline_launch_decompose2(j.devid, j.st, level, hf[s], hf[s + 1], w, h, 1 << s);
+      s++;
+      level = residual = hf[s];
+      continue;
+    }
+#endif
+    float4 *low = chain ? hf[s] : lf[s % 2];
+    if(p3) err = bspline_launch_decompose3(j.devid, j.st, level, first && s == 0, (float *)low, w, h, 1 << s, alpha_flag);
+    else err = bspline_launch_decompose(j.devid, j.st, level, chain ? nullptr : hf[s], low, w, h, 1 << s, alpha_flag);
+    level = low;
+    residual = low;
+  }
+  float4 *pp[2] = { residual == lf[1] ? lf[0] : lf[1], residual };
+  const float4 *cur = residual;
+  int count = 0;
+  for(int s = scales - 1; s >= 0 && err == DT_HIP_SUCCESS; s--, count++)
+  {
+    pde_args_of_scale(a, j, s, s == 0 && last);
+    // chain: scale s reads the low-pass planes of scales s (hf[s - 1], or the iteration's input) and s + 1 (hf[s]) and
+    // the running sum; free to write are lf[0] and, once scale s + 1 is done, hf[s + 1]: they alternate
+    float4 *to = (s == 0) ? dst : (chain ? (count % 2 == 0 ? lf[0] : hf[s + 1]) : pp[count % 2]);
+    {
+      launch_scope ls(j.devid, "diffuse_pde");
+      if(a.mult <= PDE_SHARED_MULT && !j.per_row)
+      {
+        const float4 *const h0 = chain ? (s == 0 ? src : hf[s - 1]) : hf[s], *const h1 = chain ? hf[s] : nullptr;
+        const bool dma = chain && a.mult <= PDE_DMA_MAX_MULT && !j.no_dma;
+        // (three-float planes: the final pass is the one that writes the module's float4 output)
+        pde_strip_launch(j, a, p3, first && s == 0, chain, dma, h0, h1, cur, to, p3 ? (s == 0 && last) : s == 0);
+      }
+      else
+      {
+        // gridDim.x padded to a multiple of 8: a column block stays on one XCD, the rows above and below hit its L2
+        const int rows = (h <= a.mult) ? h : ((h + a.mult - 1) / a.mult) * a.mult;
+        const dim3 grid(xcd_pad((w + 255) / 256), rows);
+        if(a.mult <= PDE_SHARED_MULT)
+          diffuse_pde<true><<<grid, 256, (size_t)3 * (256 + 2 * a.mult) * sizeof(float4), j.st>>>(hf[s], cur, to, a, s == 0, mask);
+        else
+          diffuse_pde<false><<<grid, 256, 0, j.st>>>(hf[s], cur, to, a, s == 0, mask);
+      }
+    }
+    err = check_launch("diffuse_pde");
+    cur = to;
+  }
+  return err;
+}
+
+// The module: the planes, the inpainted copy where a threshold asks for one, then the sequences of iterations
 static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diffuse_data_t *d, int first_row, dt_hip_mem_t dev_in,
                        dt_hip_mem_t dev_out, const dt_hip_lab_data_t *post_lab)
 {
@@ -1003,54 +1240,25 @@ static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diff
   const int w = piece->roi_out.width, h = piece->roi_out.height;
   if(w <= 0 || h <= 0) return DT_HIP_SUCCESS;
   if(!(d->iscale > 0.0f) || !(piece->roi_in.scale > 0.0)) return DT_HIP_INVALID_ARG;
-  const size_t plane = (size_t)w * h * sizeof(float4);
-  const float zoom = (float)(d->iscale / piece->roi_in.scale);
-  const int scales = scales_of(piece, d);
-  const int it_req = (int)ceilf((float)d->iterations);
-  const int iterations = it_req > 1 ? it_req : 1;
-
-  // planes: HF[scales], two low-pass ping-pong, two iteration ping-pong (diffuse.c:1167-1195)
-  // LF chain (every scale on the strip kernel): hf[s] holds the LOW-pass plane of scale s + 1 instead, nothing stores a
-  // high-frequency plane, and one plane besides them serves the synthesis' ping-pong (a plane fewer than the reference)
   static const bool per_row_pde = measuring_env("ANSEL_HIP_PDE_PER_ROW") != nullptr; // the per-row kernel, for A/B timing
   static const bool hf_planes = measuring_env("ANSEL_HIP_DIFFUSE_HF_PLANES") != nullptr; // the stored-HF path, for A/B timing
   static const bool no_dma = measuring_env("ANSEL_HIP_PDE_NO_DMA") != nullptr; // the rows through registers (round 4's fetch), for A/B timing
-  const bool lf_chain = !per_row_pde && !hf_planes && (1 << (scales - 1)) <= PDE_SHARED_MULT;
-  float4 *hf[DIFFUSE_MAX_SCALES] = { nullptr };
-  float4 *lf[2] = { nullptr, nullptr }, *tmp[2] = { nullptr, nullptr };
-  bool ok = true;
-  for(int s = 0; s < scales; s++) ok &= (hf[s] = (float4 *)dt_hip_alloc_device_buffer(devid, plane)) != nullptr;
-  for(int k = 0; k < (lf_chain ? 1 : 2); k++) ok &= (lf[k] = (float4 *)dt_hip_alloc_device_buffer(devid, plane)) != nullptr;
-  if(iterations > 1)
-    for(int k = 0; k < 2 && k < iterations - 1; k++)
-      ok &= (tmp[k] = (float4 *)dt_hip_alloc_device_buffer(devid, plane)) != nullptr;
-  int err = ok ? DT_HIP_SUCCESS : DT_HIP_SYSMEM_ALLOCATION;
-
+  const int it_req = (int)ceilf((float)d->iterations);
+  diffuse_job_t j;
+  j.devid = devid;
+  j.st = stream_of(devid);
+  j.d = d;
+  j.post_lab = post_lab;
+  j.w = w, j.h = h;
+  j.scales = scales_of(piece, d);
+  j.iterations = it_req > 1 ? it_req : 1;
+  j.zoom = (float)(d->iscale / piece->roi_in.scale);
+  j.lf_chain = !per_row_pde && !hf_planes && (1 << (j.scales - 1)) <= PDE_SHARED_MULT;
+  j.per_row = per_row_pde, j.no_dma = no_dma;
+  const int iterations = j.iterations;
   pde_args a;
-  memset(&a, 0, sizeof(a));
-  a.width = w;
-  a.height = h;
-  a.wskip = measuring_env("ANSEL_HIP_PDE_NO_WSKIP") ? 0 : 1;
-  {
-    const char *const approx_env = measuring_env("ANSEL_HIP_PDE_APPROX_DIV"); // read per call: tools/pde_div_ab.py flips it
-    a.approx_div = approx_env && atoi(approx_env) != 0;
-    const char *const off_env = measuring_env("ANSEL_HIP_PDE_OFF"); // read per call: tools/pde_off_ab.py
-    a.off = off_env ? atoi(off_env) : 0;
-  }
-  const float user_aniso[4] = { d->anisotropy_first, d->anisotropy_second, d->anisotropy_third, d->anisotropy_fourth };
-  for(int k = 0; k < 4; k++)
-  {
-    a.anisotropy[k] = sqf(user_aniso[k]); // compute_anisotropy_factor(), diffuse.c:970-976
-    a.kind[k] = user_aniso[k] == 0.0f ? 0 : (user_aniso[k] > 0.0f ? 1 : 2);
-  }
-  a.same02 = a.kind[0] == a.kind[2] && a.anisotropy[0] == a.anisotropy[2];
-  a.same13 = a.kind[1] == a.kind[3] && a.anisotropy[1] == a.anisotropy[3];
-  const float regularization = powf(10.0f, d->regularization) - 1.0f; // diffuse.c:999-1000
-  a.variance_threshold = powf(10.0f, d->variance_threshold);
-  const float speed[4] = { d->first, d->second, d->third, d->fourth };
+  pde_args_of_call(a, w, h, d);
 
-  hipStream_t st = stream_of(devid);
-  const float4 *src = (const float4 *)dev_in;
   // Three-float planes (diffuse_pde_strip3, bspline_decompose_strip3): the fourth channel is +0 everywhere a pipe runs this module
   // (colorin's matrix writes 0 x + 0 y + 0 z there), and with +0 in the input's alpha every plane of the module holds +0 there
   // (the analysis of +0 is +0; a blank support updates to +0, alpha_is_blank()) and the output's alpha is +0.  Where the chain
@@ -1061,197 +1269,45 @@ static int diffuse_run(int devid, const dt_hip_piece_t *piece, const dt_hip_diff
   // is up.  The modes without a three-float kernel, the luminance mask, the dilations above PDE_DMA_MAX_MULT and the stored-HF /
   // per-row paths take the float4 launches alone.
   const int mode0 = pde_mode_of(a);
-  const bool three = err == DT_HIP_SUCCESS && lf_chain && !no_dma && !(d->threshold > 0.0f) && (1 << (scales - 1)) <= PDE_DMA_MAX_MULT &&
+  const bool in_place = iterations == 1 && dev_in == dev_out && !(d->threshold > 0.0f);
+  const bool three = j.lf_chain && !no_dma && !(d->threshold > 0.0f) && (1 << (j.scales - 1)) <= PDE_DMA_MAX_MULT &&
                      !(iterations == 1 && dev_in == dev_out) && !measuring_env("ANSEL_HIP_PDE_GENERIC") &&
                      (mode0 == PDE_MODE_DEBLUR || mode0 == PDE_MODE_ISOTROPIC);
-  unsigned *alpha_flag = nullptr;
-  if(three)
-  {
-    alpha_flag = (unsigned *)dt_hip_alloc_device_buffer(devid, sizeof(unsigned));
-    if(!alpha_flag) err = DT_HIP_SYSMEM_ALLOCATION;
-    else if(hipMemsetAsync(alpha_flag, 0, sizeof(unsigned), st) != hipSuccess) err = DT_HIP_DEFAULT_ERROR;
-  }
-  unsigned char *mask = nullptr;
-  float4 *inpainted = nullptr;
-  if(err == DT_HIP_SUCCESS && d->threshold > 0.0f)
+  int err = diffuse_alloc_planes(j, in_place, three);
+  unsigned *const alpha_flag = j.p.alpha_flag.as<unsigned>(); // nullptr: the float4 launches alone
+  if(err == DT_HIP_SUCCESS && alpha_flag && hipMemsetAsync(alpha_flag, 0, sizeof(unsigned), j.st) != hipSuccess) err = DT_HIP_DEFAULT_ERROR;
+  const float4 *src = (const float4 *)dev_in;
+  if(err == DT_HIP_SUCCESS && j.p.mask)
   {
     // diffuse.c:1207-1219: mask of the pixels above the threshold, noise-seeded copy as the first iteration's input
-    // (the reference reuses "temp1" for it; the second iteration's output may overwrite it, so may ours)
     const size_t np = (size_t)w * h;
-    mask = (unsigned char *)dt_hip_alloc_device_buffer(devid, np);
-    inpainted = tmp[1] ? tmp[1] : (tmp[1] = (float4 *)dt_hip_alloc_device_buffer(devid, plane));
-    if(!mask || !inpainted) err = DT_HIP_SYSMEM_ALLOCATION;
-    else
-    {
-      launch_scope ls(devid, "diffuse_inpaint");
-      diffuse_inpaint<<<pixel_grid(np), 256, 0, st>>>(src, inpainted, mask, d->threshold, np, (size_t)w, (size_t)first_row * w);
-      err = check_launch("diffuse_inpaint");
-      src = inpainted;
-    }
+    launch_scope ls(devid, "diffuse_inpaint");
+    diffuse_inpaint<<<pixel_grid(np), 256, 0, j.st>>>(src, j.p.inpainted.as<float4>(), j.p.mask.as<unsigned char>(), d->threshold, np,
+                                                      (size_t)w, (size_t)first_row * w);
+    err = check_launch("diffuse_inpaint");
+    src = j.p.inpainted.as<float4>();
   }
-  for(int seq = three ? 0 : 1; seq < 2 && err == DT_HIP_SUCCESS; seq++)
+  for(int seq = alpha_flag ? 0 : 1; seq < 2 && err == DT_HIP_SUCCESS; seq++)
   {
-  const bool p3 = seq == 0; // the three-float sequence
-  a.gate = alpha_flag;
-  a.gate_sense = p3 ? 1 : 2;
-  if(three) src = (const float4 *)dev_in; // (no luminance mask here: the input is the module's)
-  for(int it = 0; err == DT_HIP_SUCCESS && it < iterations; it++)
-  {
-    // iteration ping-pong, diffuse.c:1223-1249 (tmp[0] = "temp2", tmp[1] = "temp1")
-    float4 *dst = (it == iterations - 1) ? (float4 *)dev_out : tmp[it % 2];
-    const float4 *level = src;
-    float4 *residual = lf[0];
-    // the chain reads the iteration's input until its last pass: not when that pass writes the same plane
-    const bool chain = lf_chain && (const float4 *)dst != src;
-    if(!chain && !lf[1])
+    const bool p3 = seq == 0; // the three-float sequence
+    a.gate = alpha_flag;
+    a.gate_sense = p3 ? 1 : 2;
+    if(alpha_flag) src = (const float4 *)dev_in; // (no luminance mask here: the input is the module's)
+    for(int it = 0; err == DT_HIP_SUCCESS && it < iterations; it++)
     {
-      lf[1] = (float4 *)dt_hip_alloc_device_buffer(devid, plane);
-      if(!lf[1])
-      {
-        err = DT_HIP_SYSMEM_ALLOCATION;
-        break;
-      }
+      // iteration ping-pong, diffuse.c:1223-1249
+      float4 *dst = (it == iterations - 1) ? (float4 *)dev_out : j.p.tmp[it % 2].as<float4>();
+      err = diffuse_iteration(j, a, p3, it == 0, it == iterations - 1, src, dst);
+      src = dst;
     }
-    for(int s = 0; s < scales && err == DT_HIP_SUCCESS; s++)
-    {
-#ifdef ANSEL_HIP_MEASURING
-      // the chain keeps every low-pass plane: two scales in one pass where the pair kernel has the dilation (1 + 2, 4 + 8)
-      static const bool pairs = measuring_env("ANSEL_HIP_BSPLINE_PAIRS") != nullptr;
-      if(chain && pairs && s + 1 < scales && (s == 0 || s == 2))
-      {
-        err = bspline_launch_decompose2(devid, st, level, hf[s], hf[s + 1], w, h, 1 << s);
-        s++;
-        level = residual = hf[s];
-        continue;
-      }
-#endif
-      float4 *low = chain ? hf[s] : lf[s % 2];
-      if(p3) err = bspline_launch_decompose3(devid, st, level, it == 0 && s == 0, (float *)low, w, h, 1 << s, alpha_flag);
-      else err = bspline_launch_decompose(devid, st, level, chain ? nullptr : hf[s], low, w, h, 1 << s, alpha_flag);
-      level = low;
-      residual = low;
-    }
-    float4 *pp[2] = { residual == lf[1] ? lf[0] : lf[1], residual };
-    const float4 *cur = residual;
-    int count = 0;
-    for(int s = scales - 1; s >= 0 && err == DT_HIP_SUCCESS; s--, count++)
-    {
-      // per-band constants, diffuse.c:1053-1074
-      const float real_radius = sigma_at_step(BSPLINE_SIGMA, (unsigned)s) * zoom;
-      a.regularization = regularization / 9.0f * sqf(real_radius);
-      const float norm = expf(-sqf(real_radius - (float)d->radius_center) / sqf((float)d->radius));
-      for(int k = 0; k < 4; k++) a.abcd[k] = speed[k] * PDE_KAPPA * norm;
-      a.strength = d->sharpness * norm + 1.0f;
-      a.mult = 1 << s;
-      a.post_lab = 0;
-      if(post_lab && s == 0 && it == iterations - 1)
-      {
-        a.post_lab = 1;
-        memcpy(a.post_m, post_lab->matrix, sizeof(a.post_m));
-      }
-      // chain: scale s reads the low-pass planes of scales s (hf[s - 1], or the iteration's input) and s + 1 (hf[s]) and
-      // the running sum; free to write are lf[0] and, once scale s + 1 is done, hf[s + 1]: they alternate
-      float4 *to = (s == 0) ? dst : (chain ? (count % 2 == 0 ? lf[0] : hf[s + 1]) : pp[count % 2]);
-      const int rows = (h <= a.mult) ? h : ((h + a.mult - 1) / a.mult) * a.mult;
-      {
-        launch_scope ls(devid, "diffuse_pde");
-        // gridDim.x padded to a multiple of 8: a column block stays on one XCD, the rows above and below hit its L2
-        const dim3 grid(xcd_pad((w + 255) / 256), rows);
-        const bool per_row = per_row_pde;
-        if(a.mult <= PDE_SHARED_MULT && !per_row)
-        {
-          const int classes = h < a.mult ? h : a.mult, per_class = (h + a.mult - 1) / a.mult;
-          const int gx = (w + 255) / 256;
-          int strip = 32;
-#ifdef ANSEL_HIP_MEASURING
-          static const char *const strip_env = measuring_env("ANSEL_HIP_PDE_STRIP"); // rows a workgroup keeps its columns for, for A/B timing
-          if(strip_env) strip = atoi(strip_env);
-#endif
-          while(strip > 4 && (size_t)gx * classes * ((per_class + strip - 1) / strip) < 2048) strip /= 2;
-          const int spc = (per_class + strip - 1) / strip;
-          size_t ring = (size_t)PDE_RING * (256 + 2 * a.mult) * sizeof(float4);
-#ifdef ANSEL_HIP_MEASURING
-          // how much the kernel needs its occupancy: LDS asked for and not used (bytes), for A/B timing
-          static const char *const pad_env = measuring_env("ANSEL_HIP_PDE_LDS_PAD");
-          if(pad_env) ring += (size_t)atoi(pad_env);
-#endif
-          static const bool generic = measuring_env("ANSEL_HIP_PDE_GENERIC") != nullptr; // the kinds read at run time, for A/B timing
-          const int mode = generic ? -1 : pde_mode_of(a);
-          const dim3 sgrid(gx, classes * spc);
-          const float4 *const h0 = chain ? (s == 0 ? src : hf[s - 1]) : hf[s], *const h1 = chain ? hf[s] : nullptr;
-#define PDE_LAUNCH(HS, MD) diffuse_pde_strip<HS, MD><<<sgrid, 256, ring, st>>>(h0, h1, cur, to, a, s == 0, mask, strip, spc)
-          // the rows by LDS-DMA into per-wave landing zones behind the ring (the kernel's comment): the low-pass chain (three planes a row) at the dilations whose halo is at most a quarter of a wave
-          // (with a luminance mask the byte the row step loads makes the compiler wait for every vector-memory operation in flight,
-          // the row fetch included, in the middle of a step: masked runs keep the form -- same result -- but not its overlap)
-          const bool dma = chain && a.mult <= PDE_DMA_MAX_MULT && !no_dma;
-          const size_t ring_dma = ring + (size_t)4 * 3 * (64 + 2 * a.mult) * sizeof(float4);
-#define PDE_LAUNCH_DMA(MD) diffuse_pde_strip<true, MD, true><<<sgrid, 256, ring_dma, st>>>(h0, h1, cur, to, a, s == 0, mask, strip, spc)
-          bool launched = false;
-          if(p3)
-          {
-            // three-float planes: 12 B ring entries, and per wave a landing zone of 3 x 16 B slots (pde_dma_planes3())
-            const bool h0_4 = it == 0 && s == 0;
-            const size_t lds3 = (size_t)PDE_RING * (256 + 2 * a.mult) * 12 + (size_t)4 * 3 * (64 + 2 * a.mult) * 16;
-            const int last = s == 0 && it == iterations - 1; // the module's float4 output
-#define PDE_LAUNCH3(MD, H4) diffuse_pde_strip3<MD, H4><<<sgrid, 256, lds3, st>>>(h0, h1, cur, to, a, last, strip, spc)
-            if(mode == PDE_MODE_DEBLUR)
-            {
-              if(h0_4) PDE_LAUNCH3(PDE_MODE_DEBLUR, true);
-              else PDE_LAUNCH3(PDE_MODE_DEBLUR, false);
-            }
-            else
-            {
-              if(h0_4) PDE_LAUNCH3(PDE_MODE_ISOTROPIC, true);
-              else PDE_LAUNCH3(PDE_MODE_ISOTROPIC, false);
-            }
-#undef PDE_LAUNCH3
-            launched = true;
-          }
-#define PDE_CASE(MD)                     \
-  if(!launched && mode == (MD))          \
-  {                                      \
-    if(dma) PDE_LAUNCH_DMA(MD);          \
-    else if(chain) PDE_LAUNCH(true, MD); \
-    else PDE_LAUNCH(false, MD);          \
-    launched = true;                     \
   }
-          PDE_MODES(PDE_CASE)
-#undef PDE_CASE
-          if(!launched)
-          {
-            if(dma) PDE_LAUNCH_DMA(-1);
-            else if(chain) PDE_LAUNCH(true, -1);
-            else PDE_LAUNCH(false, -1);
-          }
-#undef PDE_LAUNCH_DMA
-#undef PDE_LAUNCH
-        }
-        else if(a.mult <= PDE_SHARED_MULT)
-          diffuse_pde<true><<<grid, 256, (size_t)3 * (256 + 2 * a.mult) * sizeof(float4), st>>>(hf[s], cur, to, a, s == 0, mask);
-        else
-          diffuse_pde<false><<<grid, 256, 0, st>>>(hf[s], cur, to, a, s == 0, mask);
-      }
-      err = check_launch("diffuse_pde");
-      cur = to;
-    }
-    src = dst;
-  }
-  }
-  for(int s = 0; s < scales; s++)
-    if(hf[s]) dt_hip_release_mem_object(hf[s]);
-  for(int k = 0; k < 2; k++)
-  {
-    if(lf[k]) dt_hip_release_mem_object(lf[k]);
-    if(tmp[k]) dt_hip_release_mem_object(tmp[k]);
-  }
-  if(mask) dt_hip_release_mem_object(mask);
   if(alpha_flag)
   {
-    if(g_diffuse_probe && err == DT_HIP_SUCCESS && hipMemcpyAsync(g_diffuse_probe, alpha_flag, sizeof(unsigned), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    if(g_diffuse_probe && err == DT_HIP_SUCCESS
+       && hipMemcpyAsync(g_diffuse_probe, alpha_flag, sizeof(unsigned), hipMemcpyDeviceToDevice, j.st) != hipSuccess)
       err = DT_HIP_DEFAULT_ERROR;
-    dt_hip_release_mem_object(alpha_flag);
   }
-  else if(g_diffuse_probe && err == DT_HIP_SUCCESS && hipMemsetAsync(g_diffuse_probe, 0xff, sizeof(unsigned), st) != hipSuccess)
+  else if(g_diffuse_probe && err == DT_HIP_SUCCESS && hipMemsetAsync(g_diffuse_probe, 0xff, sizeof(unsigned), j.st) != hipSuccess)
     err = DT_HIP_DEFAULT_ERROR;
   return err;
 }

@@ -180,22 +180,19 @@ int resample_launch(int devid, const dt_hip_piece_t *piece, const int kind, dt_h
   const size_t o_vi = o; memcpy(&blob[o], v.index.data(), v.index.size() * 4); o += v.index.size();
   const size_t o_hk = o; memcpy(&blob[o], h.kernel.data(), h.kernel.size() * 4); o += h.kernel.size();
   const size_t o_vk = o; memcpy(&blob[o], v.kernel.data(), v.kernel.size() * 4); o += v.kernel.size();
-  int *dev = (int *)dt_hip_alloc_device_buffer(devid, blob.size() * 4);
-  if(!dev) return DT_HIP_SYSMEM_ALLOCATION;
+  const dev_buf_t plan = dev_buf_t::alloc(devid, blob.size() * 4);
+  if(!plan) return DT_HIP_SYSMEM_ALLOCATION;
+  int *const dev = plan.as<int>();
   hipStream_t s = stream_of(devid);
   if(hipMemcpyAsync(dev, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess
      || hipStreamSynchronize(s) != hipSuccess) // blob is a stack-lifetime host buffer
-  {
-    dt_hip_release_mem_object(dev);
     return DT_HIP_DEFAULT_ERROR;
-  }
   plan_dev ph = { dev + o_hl, dev + o_hs, dev + o_hi, (const float *)(dev + o_hk) };
   plan_dev pv = { dev + o_vl, dev + o_vs, dev + o_vi, (const float *)(dev + o_vk) };
   {
     launch_scope ls(devid, tag);
     resample<<<pixel_grid((size_t)ow * oh), 256, 0, s>>>((const float4 *)dev_in, (float4 *)dev_out, iw, ow, oh, ph, pv);
   }
-  dt_hip_release_mem_object(dev);
   return check_launch(tag);
 }
 

@@ -264,8 +264,9 @@ int guided_filter_launch(int devid, const float4 *guide, float *mask, int width,
     }
   // the input of every tile is the mask as it was: a copy, like the reference's mask_bak
   const size_t np = (size_t)width * height;
-  float *bak = (float *)dt_hip_alloc_device_buffer(devid, np * sizeof(float));
-  if(!bak) return DT_HIP_SYSMEM_ALLOCATION;
+  const dev_buf_t bak_buf = dev_buf_t::alloc(devid, np * sizeof(float));
+  if(!bak_buf) return DT_HIP_SYSMEM_ALLOCATION;
+  float *const bak = bak_buf.as<float>();
   int err = DT_HIP_SUCCESS;
   if(hipMemcpyAsync(bak, mask, np * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) err = DT_HIP_DEFAULT_ERROR;
   // the batch budget follows the device: batching does not change the result, so a device with little free memory (or
@@ -291,9 +292,12 @@ int guided_filter_launch(int devid, const float4 *guide, float *mask, int width,
       last++;
     }
     const unsigned nt = (unsigned)(last - first);
-    float *A = (float *)dt_hip_alloc_device_buffer(devid, floats * sizeof(float));
-    float *B = (float *)dt_hip_alloc_device_buffer(devid, floats * sizeof(float));
-    gf_tile *dt = (gf_tile *)dt_hip_alloc_device_buffer(devid, nt * sizeof(gf_tile));
+    // the batch's planes and tile table: back to the pool at the end of each round
+    const dev_buf_t A_buf = dev_buf_t::alloc(devid, floats * sizeof(float));
+    const dev_buf_t B_buf = dev_buf_t::alloc(devid, floats * sizeof(float));
+    const dev_buf_t dt_buf = dev_buf_t::alloc(devid, nt * sizeof(gf_tile));
+    float *const A = A_buf.as<float>(), *const B = B_buf.as<float>();
+    gf_tile *const dt = dt_buf.as<gf_tile>();
     if(!A || !B || !dt) err = DT_HIP_SYSMEM_ALLOCATION;
     else if(hipMemcpyAsync(dt, tiles.data() + first, nt * sizeof(gf_tile), hipMemcpyHostToDevice, s) != hipSuccess
             || hipStreamSynchronize(s) != hipSuccess) // `tiles` is a stack-lifetime host buffer
@@ -318,12 +322,8 @@ int guided_filter_launch(int devid, const float4 *guide, float *mask, int width,
       gf_apply<<<dim3(gpix, nt), 256, 0, s>>>(guide, B, mask, dt, width, guide_weight, minv, maxv);
       err = check_launch("guided_filter");
     }
-    if(A) dt_hip_release_mem_object(A);
-    if(B) dt_hip_release_mem_object(B);
-    if(dt) dt_hip_release_mem_object(dt);
     first = last;
   }
-  dt_hip_release_mem_object(bak);
   return err;
 }
 

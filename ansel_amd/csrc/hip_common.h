@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "ansel_hip.h"
+#include "dev_buf.h"
 
 // The A/B switches of the kernels' development (superseded kernel versions, roles switched off, clock reads) exist in the
 // MEASURING build only: `python -m ansel_amd.build --measuring` compiles every translation unit with

@@ -797,40 +797,29 @@ extern "C" int dt_hip_export_jpeg(int devid, int width, int height, const dt_hip
   const size_t sz_coef = (size_t)g.nblocks * 128, sz_len = (size_t)g.nblocks * 4, sz_part = (size_t)nwg * 8;
   const size_t sz_words = (size_t)(max_bits / 32 + 2) * 4, sz_cnt = (size_t)max_chunks * 4 + 4;
   const size_t sz_small = sizeof(tables_t) + sizeof(state_t) + 4 * JH_NSYM * 4;
-  dt_hip_mem_t m_coef = dt_hip_alloc_device_buffer(devid, sz_coef);
-  dt_hip_mem_t m_len = dt_hip_alloc_device_buffer(devid, sz_len);
-  dt_hip_mem_t m_part = dt_hip_alloc_device_buffer(devid, sz_part);
-  dt_hip_mem_t m_words = dt_hip_alloc_device_buffer(devid, sz_words);
-  dt_hip_mem_t m_cnt = dt_hip_alloc_device_buffer(devid, sz_cnt);
-  dt_hip_mem_t m_small = dt_hip_alloc_device_buffer(devid, sz_small);
-  dt_hip_mem_t m_fixed = dt_hip_alloc_device_buffer(devid, fixed.size());
-  auto release = [&]() {
-    for(dt_hip_mem_t m : { m_coef, m_len, m_part, m_words, m_cnt, m_small, m_fixed }) dt_hip_release_mem_object(m);
-  };
-  if(!m_coef || !m_len || !m_part || !m_words || !m_cnt || !m_small || !m_fixed)
-  {
-    release();
-    return DT_HIP_DEFAULT_ERROR;
-  }
-  tables_t *tab = (tables_t *)m_small;
-  state_t *st = (state_t *)((uint8_t *)m_small + sizeof(tables_t));
-  uint32_t *freq = (uint32_t *)((uint8_t *)m_small + sizeof(tables_t) + sizeof(state_t));
+  const dev_buf_t m_coef = dev_buf_t::alloc(devid, sz_coef);
+  const dev_buf_t m_len = dev_buf_t::alloc(devid, sz_len);
+  const dev_buf_t m_part = dev_buf_t::alloc(devid, sz_part);
+  const dev_buf_t m_words = dev_buf_t::alloc(devid, sz_words);
+  const dev_buf_t m_cnt = dev_buf_t::alloc(devid, sz_cnt);
+  const dev_buf_t m_small = dev_buf_t::alloc(devid, sz_small);
+  const dev_buf_t m_fixed = dev_buf_t::alloc(devid, fixed.size());
+  if(!m_coef || !m_len || !m_part || !m_words || !m_cnt || !m_small || !m_fixed) return DT_HIP_DEFAULT_ERROR;
+  tables_t *tab = m_small.as<tables_t>();
+  state_t *st = (state_t *)(m_small.as<uint8_t>() + sizeof(tables_t));
+  uint32_t *freq = (uint32_t *)(m_small.as<uint8_t>() + sizeof(tables_t) + sizeof(state_t));
   hipStream_t s = stream_of(devid);
-  int err = upload_small(devid, m_fixed, fixed.data(), fixed.size());
-  if(err != DT_HIP_SUCCESS)
-  {
-    release();
-    return err;
-  }
+  const int err = upload_small(devid, m_fixed.ptr(), fixed.data(), fixed.size());
+  if(err != DT_HIP_SUCCESS) return err;
   {
     launch_scope ls(devid, "jpeg_fdct");
-    jpeg_fdct<<<nwg, JPEG_THREADS, 0, s>>>((const uint32_t *)dev_in_rgba8, g, q, (int16_t *)m_coef);
+    jpeg_fdct<<<nwg, JPEG_THREADS, 0, s>>>((const uint32_t *)dev_in_rgba8, g, q, m_coef.as<int16_t>());
   }
   if(d->optimize_coding)
   {
     launch_scope ls(devid, "jpeg_stats");
     (void)hipMemsetAsync(freq, 0, 4 * JH_NSYM * 4, s);
-    jpeg_stats<<<nwg, JPEG_THREADS, 0, s>>>((const int16_t *)m_coef, g, freq);
+    jpeg_stats<<<nwg, JPEG_THREADS, 0, s>>>(m_coef.as<const int16_t>(), g, freq);
   }
   {
     launch_scope ls(devid, "jpeg_tables");
@@ -838,25 +827,24 @@ extern "C" int dt_hip_export_jpeg(int devid, int width, int height, const dt_hip
   }
   {
     launch_scope ls(devid, "jpeg_lengths");
-    jpeg_lengths<<<nwg, JPEG_THREADS, 0, s>>>((const int16_t *)m_coef, g, tab, (uint32_t *)m_len, (uint64_t *)m_part);
-    jpeg_scan_partials<<<1, JPEG_THREADS, 0, s>>>((uint64_t *)m_part, nwg, st);
+    jpeg_lengths<<<nwg, JPEG_THREADS, 0, s>>>(m_coef.as<const int16_t>(), g, tab, m_len.as<uint32_t>(), m_part.as<uint64_t>());
+    jpeg_scan_partials<<<1, JPEG_THREADS, 0, s>>>(m_part.as<uint64_t>(), nwg, st);
   }
   {
     launch_scope ls(devid, "jpeg_emit");
-    jpeg_zero<<<stream_grid(max_bits / 32 + 1, JPEG_THREADS), JPEG_THREADS, 0, s>>>((uint32_t *)m_words, st);
-    jpeg_emit<<<nwg, JPEG_THREADS, 0, s>>>((const int16_t *)m_coef, g, tab, (const uint32_t *)m_len,
-                                           (const uint64_t *)m_part, (uint32_t *)m_words);
+    jpeg_zero<<<stream_grid(max_bits / 32 + 1, JPEG_THREADS), JPEG_THREADS, 0, s>>>(m_words.as<uint32_t>(), st);
+    jpeg_emit<<<nwg, JPEG_THREADS, 0, s>>>(m_coef.as<const int16_t>(), g, tab, m_len.as<const uint32_t>(),
+                                           m_part.as<const uint64_t>(), m_words.as<uint32_t>());
   }
   {
     launch_scope ls(devid, "jpeg_stuff");
     const unsigned cg = (unsigned)std::min<uint64_t>(max_chunks, 2048);
-    jpeg_ff_count<<<cg, JPEG_THREADS, 0, s>>>((const uint32_t *)m_words, st, (uint32_t *)m_cnt);
-    jpeg_ff_scan<<<1, JPEG_THREADS, 0, s>>>((uint32_t *)m_cnt, st, tab, (uint32_t)fixed.size(), d->capacity,
+    jpeg_ff_count<<<cg, JPEG_THREADS, 0, s>>>(m_words.as<const uint32_t>(), st, m_cnt.as<uint32_t>());
+    jpeg_ff_scan<<<1, JPEG_THREADS, 0, s>>>(m_cnt.as<uint32_t>(), st, tab, (uint32_t)fixed.size(), d->capacity,
                                              (uint8_t *)dev_out);
-    jpeg_compact<<<cg, JPEG_THREADS, 0, s>>>((const uint32_t *)m_words, st, (const uint32_t *)m_cnt, (uint8_t *)dev_out);
-    jpeg_headers<<<1, JPEG_THREADS, 0, s>>>((const uint8_t *)m_fixed, (uint32_t)fixed.size(), tab, st,
+    jpeg_compact<<<cg, JPEG_THREADS, 0, s>>>(m_words.as<const uint32_t>(), st, m_cnt.as<const uint32_t>(), (uint8_t *)dev_out);
+    jpeg_headers<<<1, JPEG_THREADS, 0, s>>>(m_fixed.as<const uint8_t>(), (uint32_t)fixed.size(), tab, st,
                                              (uint8_t *)dev_out);
   }
-  release();
   return check_launch("export_jpeg");
 }

@@ -202,13 +202,17 @@ int local_laplacian_launch(int devid, const float4 *in, float4 *out, int wd, int
   const int support = 1 << top_level;
   const int w = 2 * support + wd, h = 2 * support + ht;
   float *padded[LL_MAX_LEVELS] = { nullptr }, *output[LL_MAX_LEVELS] = { nullptr }, *buf[LL_NUM_GAMMA][LL_MAX_LEVELS] = { { nullptr } };
+  // the planes of the three pyramids belong to `held` until this function returns
+  dev_buf_t held[(2 + LL_NUM_GAMMA) * LL_MAX_LEVELS];
+  int nheld = 0;
+  auto plane = [&](const size_t bytes) { return (held[nheld++] = dev_buf_t::alloc(devid, bytes)).as<float>(); };
   bool ok = true;
   for(int l = 0; l <= top_level; l++)
   {
     const size_t bytes = (size_t)dl(w, l) * dl(h, l) * sizeof(float);
-    if(l < top_level) ok &= (padded[l] = (float *)dt_hip_alloc_device_buffer(devid, bytes)) != nullptr;
-    ok &= (output[l] = (float *)dt_hip_alloc_device_buffer(devid, bytes)) != nullptr;
-    for(int k = 0; k < LL_NUM_GAMMA; k++) ok &= (buf[k][l] = (float *)dt_hip_alloc_device_buffer(devid, bytes)) != nullptr;
+    if(l < top_level) ok &= (padded[l] = plane(bytes)) != nullptr;
+    ok &= (output[l] = plane(bytes)) != nullptr;
+    for(int k = 0; k < LL_NUM_GAMMA; k++) ok &= (buf[k][l] = plane(bytes)) != nullptr;
   }
   int err = ok ? DT_HIP_SUCCESS : DT_HIP_SYSMEM_ALLOCATION;
   hipStream_t s = stream_of(devid);
@@ -272,13 +276,6 @@ int local_laplacian_launch(int devid, const float4 *in, float4 *out, int wd, int
       ll_finish<<<pixel_grid((size_t)wd * ht), 256, 0, s>>>(in, (float *)out, output[0], wd, ht, w, support);
     }
     err = check_launch("local laplacian");
-  }
-  for(int l = 0; l <= top_level; l++)
-  {
-    if(padded[l]) dt_hip_release_mem_object(padded[l]);
-    if(output[l]) dt_hip_release_mem_object(output[l]);
-    for(int k = 0; k < LL_NUM_GAMMA; k++)
-      if(buf[k][l]) dt_hip_release_mem_object(buf[k][l]);
   }
   return err;
 }

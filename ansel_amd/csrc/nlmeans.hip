@@ -1249,25 +1249,23 @@ int nlmeans_core_launch(int devid, const float4 *in, float4 *out, int width, int
   std::vector<unsigned char> host_blob(patch_bytes + order_bytes);
   memcpy(host_blob.data(), patches.data(), patch_bytes);
   if(order_bytes) memcpy(host_blob.data() + patch_bytes, order.data(), order_bytes);
-  int2 *dev_patches = (int2 *)dt_hip_alloc_device_buffer(devid, host_blob.size());
+  const dev_buf_t patches_buf = dev_buf_t::alloc(devid, host_blob.size());
+  int2 *const dev_patches = patches_buf.as<int2>();
   if(!dev_patches) return DT_HIP_SYSMEM_ALLOCATION;
   // (through the runtime's pinned staging ring: `host_blob` is a stack-lifetime buffer, and waiting for the stream here was a host
   // meeting in the middle of every frame)
-  if(const int uerr = upload_small(devid, dev_patches, host_blob.data(), host_blob.size()); uerr != DT_HIP_SUCCESS)
-  {
-    dt_hip_release_mem_object(dev_patches);
-    return uerr;
-  }
+  if(const int uerr = upload_small(devid, dev_patches, host_blob.data(), host_blob.size()); uerr != DT_HIP_SUCCESS) return uerr;
   const int *const dev_order = (const int *)((const unsigned char *)dev_patches + patch_bytes);
   // the head's export: one column-sum row per chunk and offset (NLT_SEED_PITCH floats: ~14.5 B per pixel of the frame, written
   // once, read once -- the module's one per-call device allocation beyond in + out, dt_hip_iop_nlmeans_tiling()).  A frame
   // it does not fit beside keeps the second version's body, which needs nothing of the kind
-  float *seeds = nullptr;
+  dev_buf_t seeds_buf;
   if(tall)
   {
-    seeds = (float *)dt_hip_alloc_device_buffer(devid, (size_t)nchunks * a.npatch * NLT_SEED_PITCH * sizeof(float));
-    if(!seeds) tall = false;
+    seeds_buf = dev_buf_t::alloc(devid, (size_t)nchunks * a.npatch * NLT_SEED_PITCH * sizeof(float));
+    if(!seeds_buf) tall = false;
   }
+  float *const seeds = seeds_buf.as<float>();
   // the opt-in to more than 64 KB of LDS, before anything is launched: a failure leaves nothing behind
   hipError_t attr_err = hipSuccess;
   if(tall)
@@ -1279,8 +1277,6 @@ int nlmeans_core_launch(int devid, const float4 *in, float4 *out, int width, int
   if(attr_err != hipSuccess)
   {
     set_last_error("%s:%d hipFuncSetAttribute(nlm_chunks): %s", __FILE__, __LINE__, hipGetErrorString(attr_err));
-    if(seeds) dt_hip_release_mem_object(seeds);
-    dt_hip_release_mem_object(dev_patches);
     return DT_HIP_DEFAULT_ERROR;
   }
   {
@@ -1322,8 +1318,6 @@ int nlmeans_core_launch(int devid, const float4 *in, float4 *out, int width, int
       kt_in<<<(unsigned)(nchunks - n_border), NLT_THREADS, tail_bytes, s>>>(in, out, a, dev_patches, dev_order, n_border, seeds);
     err = check_launch("nlm_tail");
   }
-  if(seeds) dt_hip_release_mem_object(seeds);
-  dt_hip_release_mem_object(dev_patches);
   return err;
 }
 

@@ -508,7 +508,8 @@ int dt_hip_peer_selftest(const int *devids, int n)
     const int k = pair;
     const int a = devids[ka], b = devids[kb];
     for(size_t i = 0; i < N; i++) pattern[i] = (unsigned)(i * 2654435761u + (unsigned)k);
-    unsigned *da = (unsigned *)dt_hip_alloc_device_buffer(a, N * 4), *db = (unsigned *)dt_hip_alloc_device_buffer(b, N * 4);
+    const dev_buf_t da_buf = dev_buf_t::alloc(a, N * 4), db_buf = dev_buf_t::alloc(b, N * 4);
+    unsigned *const da = da_buf.as<unsigned>(), *const db = db_buf.as<unsigned>();
     int err = (da && db) ? DT_HIP_SUCCESS : DT_HIP_SYSMEM_ALLOCATION;
     hipEvent_t ev = nullptr;
     if(err == DT_HIP_SUCCESS)
@@ -542,8 +543,6 @@ int dt_hip_peer_selftest(const int *devids, int n)
       (void)hipStreamSynchronize(sa);
     }
     if(ev) (void)hipEventDestroy(ev);
-    if(da) dt_hip_release_mem_object(da);
-    if(db) dt_hip_release_mem_object(db);
     if(err != DT_HIP_SUCCESS)
     {
       (void)hipGetLastError();

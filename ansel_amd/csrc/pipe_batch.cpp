@@ -14,15 +14,15 @@ extern "C" {
 
 struct batch_slot_t
 {
-  dt_hip_mem_t d_in, d_out;
-  hipEvent_t up, done, down;
-  hipEvent_t kstart; // in front of the frame's first kernel (timed with `done` and `down`: the upload policy below)
-  bool in_flight;
+  dev_buf_t d_in, d_out; // back to the pool with the slot (dt_hip_batch_free())
+  hipEvent_t up = nullptr, done = nullptr, down = nullptr;
+  hipEvent_t kstart = nullptr; // in front of the frame's first kernel (timed with `done` and `down`: the upload policy below)
+  bool in_flight = false;
   // with a writer: the frame's place in the stream, its host buffer, and what became of it (guarded by the batch's mutex)
-  long seq;
-  void *host_out;
-  bool written;
-  int write_err;
+  long seq = 0;
+  void *host_out = nullptr;
+  bool written = false;
+  int write_err = 0;
 };
 
 struct dt_hip_batch_t
@@ -96,12 +96,11 @@ dt_hip_batch_t *dt_hip_batch_new(dt_hip_pipe_t *pipe, int depth, size_t in_bytes
   for(int k = 0; k < depth && ok; k++)
   {
     batch_slot_t sl;
-    memset(&sl, 0, sizeof(sl));
-    sl.d_in = dt_hip_alloc_device_buffer(pipe->devid, in_bytes);
-    sl.d_out = dt_hip_alloc_device_buffer(pipe->devid, out_bytes);
+    sl.d_in = dev_buf_t::alloc(pipe->devid, in_bytes);
+    sl.d_out = dev_buf_t::alloc(pipe->devid, out_bytes);
     ok = sl.d_in && sl.d_out && hipEventCreateWithFlags(&sl.up, hipEventDisableTiming) == hipSuccess
          && hipEventCreate(&sl.kstart) == hipSuccess && hipEventCreate(&sl.done) == hipSuccess && hipEventCreate(&sl.down) == hipSuccess;
-    b->slots.push_back(sl);
+    b->slots.push_back(std::move(sl));
   }
   if(!ok)
   {
@@ -127,13 +126,11 @@ void dt_hip_batch_free(dt_hip_batch_t *b)
     b->writer_thread.join();
   }
   // a submit that failed half way leaves its upload (or download) enqueued without marking the slot in flight:
-  // the copy streams must be idle before the slot buffers go back to the pool
+  // the copy streams must be idle before the slot buffers go back to the pool (with `delete b`)
   if(b->s_up) (void)hipStreamSynchronize(b->s_up);
   if(b->s_down) (void)hipStreamSynchronize(b->s_down);
   for(batch_slot_t &sl : b->slots)
   {
-    if(sl.d_in) dt_hip_release_mem_object(sl.d_in);
-    if(sl.d_out) dt_hip_release_mem_object(sl.d_out);
     if(sl.up) (void)hipEventDestroy(sl.up);
     if(sl.kstart) (void)hipEventDestroy(sl.kstart);
     if(sl.done) (void)hipEventDestroy(sl.done);
@@ -242,16 +239,16 @@ int dt_hip_batch_submit(dt_hip_batch_t *b, const void *host_in, void *host_out)
     return w;
   }
   hipStream_t compute = stream_of(b->pipe->devid);
-  ANSEL_HIP_CHECK(hipMemcpyAsync(sl.d_in, host_in, b->in_bytes, hipMemcpyHostToDevice, b->s_up));
+  ANSEL_HIP_CHECK(hipMemcpyAsync(sl.d_in.ptr(), host_in, b->in_bytes, hipMemcpyHostToDevice, b->s_up));
   ANSEL_HIP_CHECK(hipEventRecord(sl.up, b->s_up));
   if(b->host_awaits_upload) ANSEL_HIP_CHECK(hipEventSynchronize(sl.up)); // (batch_update_policy(): which, and why)
   else ANSEL_HIP_CHECK(hipStreamWaitEvent(compute, sl.up, 0));
   ANSEL_HIP_CHECK(hipEventRecord(sl.kstart, compute));
-  const int err = dt_hip_pipe_process(b->pipe, sl.d_in, sl.d_out);
+  const int err = dt_hip_pipe_process(b->pipe, sl.d_in.ptr(), sl.d_out.ptr());
   if(err != DT_HIP_SUCCESS) return err;
   ANSEL_HIP_CHECK(hipEventRecord(sl.done, compute));
   ANSEL_HIP_CHECK(hipStreamWaitEvent(b->s_down, sl.done, 0));
-  ANSEL_HIP_CHECK(hipMemcpyAsync(host_out, sl.d_out, b->out_bytes, hipMemcpyDeviceToHost, b->s_down));
+  ANSEL_HIP_CHECK(hipMemcpyAsync(host_out, sl.d_out.ptr(), b->out_bytes, hipMemcpyDeviceToHost, b->s_down));
   ANSEL_HIP_CHECK(hipEventRecord(sl.down, b->s_down));
   sl.in_flight = true;
   if(b->writer)

@@ -192,6 +192,7 @@ int raw_group_launch(int devid, const raw_group_t &g, dt_hip_mem_t dev_in, dt_hi
   }
   a.has_clip = g.has_highlights;
   hipStream_t s = stream_of(devid);
+  dev_buf_t journal_buf; // the caller's (deferred: it resolves the journal later) or ours
   hl_journal *journal = nullptr;
   if(g.has_highlights)
   {
@@ -200,13 +201,10 @@ int raw_group_launch(int devid, const raw_group_t &g, dt_hip_mem_t dev_in, dt_hi
       pmax[c] = (g.highlights_piece.processed_maximum[c] > 0.f) ? g.highlights_piece.processed_maximum[c] : 1.0f;
     a.clip = g.highlights.clip * fminf(pmax[0], fminf(pmax[1], pmax[2]));
     a.threshold = a.clip;
-    journal = deferred ? (hl_journal *)deferred : (hl_journal *)dt_hip_alloc_device_buffer(devid, sizeof(hl_journal));
+    journal_buf = deferred ? dev_buf_t::borrow(deferred) : dev_buf_t::alloc(devid, sizeof(hl_journal));
+    journal = journal_buf.as<hl_journal>();
     if(!journal) return DT_HIP_SYSMEM_ALLOCATION;
-    if(hipMemsetAsync(journal, 0, sizeof(hl_journal), s) != hipSuccess)
-    {
-      if(!deferred) dt_hip_release_mem_object(journal);
-      return DT_HIP_DEFAULT_ERROR;
-    }
+    if(hipMemsetAsync(journal, 0, sizeof(hl_journal), s) != hipSuccess) return DT_HIP_DEFAULT_ERROR;
   }
   const size_t work = (size_t)(a.width / 4) * a.height;
   {
@@ -216,11 +214,7 @@ int raw_group_launch(int devid, const raw_group_t &g, dt_hip_mem_t dev_in, dt_hi
     else
       raw_chain<float><<<stream_grid(work, 256), 256, 0, s>>>((const float *)dev_in, (float *)dev_out, a, journal);
   }
-  if(journal && !deferred)
-  {
-    highlights_resolve_launch(devid, (float *)dev_out, journal);
-    dt_hip_release_mem_object(journal);
-  }
+  if(journal_buf.owned()) highlights_resolve_launch(devid, (float *)dev_out, journal);
   return check_launch("raw_chain");
 }
 

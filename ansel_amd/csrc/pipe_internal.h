@@ -1,8 +1,9 @@
 // pipe_internal.h -- what the translation units of the executor share: the module table, the node list with its plan,
-// and the handle of a device buffer (pipe.cpp, pipe_batch.cpp, pipe_bands.cpp, pipe_tiling.cpp).
+// (pipe.cpp, pipe_batch.cpp, pipe_bands.cpp, pipe_tiling.cpp).
 // Not part of the C-ABI (that is include/ansel_hip.h).
 #pragma once
 #include "hip_common.h"
+#include "dev_buf.h"
 #include "pipe_fused.h"
 
 #include <string>
@@ -86,48 +87,6 @@ int make_node(node_t &n, const char *who, const char *name, const dt_hip_piece_t
 size_t out_bytes(const node_t &n);
 static inline int run_single(int devid, const node_t &n, dt_hip_mem_t in, dt_hip_mem_t out) { return k_ops[n.op].run(devid, n, in, out); }
 static inline int band_halo_rows(const node_t &n) { return k_ops[n.op].halo_rows ? k_ops[n.op].halo_rows(n) : 0; }
-
-// A device buffer of a walk: the allocation, the byte offset of the view into it that the launches read or write (a band's
-// own rows inside a [halo][rows][halo] layout), and whether the handle owns the allocation.  An owned allocation goes back to
-// the runtime's pool when the handle is released, assigned to or destroyed (stream-ordered: safe behind the launches that
-// are enqueued); a borrowed one (the caller's dev_in / dev_out) is left alone.
-class dev_buf_t
-{
-  dt_hip_mem_t base_ = nullptr;
-  size_t offset_ = 0;
-  bool owned_ = false;
-
-public:
-  dev_buf_t() = default;
-  dev_buf_t(dt_hip_mem_t base, bool owned, size_t offset = 0) : base_(base), offset_(offset), owned_(owned) {}
-  // from the pool; empty when the pool has nothing to give
-  static dev_buf_t alloc(int devid, size_t bytes, size_t offset = 0) { return dev_buf_t(dt_hip_alloc_device_buffer(devid, bytes), true, offset); }
-  static dev_buf_t borrow(dt_hip_mem_t base) { return dev_buf_t(base, false); }
-  dev_buf_t(dev_buf_t &&o) noexcept : base_(o.base_), offset_(o.offset_), owned_(o.owned_) { o.base_ = nullptr; }
-  dev_buf_t &operator=(dev_buf_t &&o) noexcept
-  {
-    if(this != &o)
-    {
-      release();
-      base_ = o.base_, offset_ = o.offset_, owned_ = o.owned_;
-      o.base_ = nullptr;
-    }
-    return *this;
-  }
-  dev_buf_t(const dev_buf_t &) = delete;
-  dev_buf_t &operator=(const dev_buf_t &) = delete;
-  ~dev_buf_t() { release(); }
-  void release()
-  {
-    if(base_ && owned_) dt_hip_release_mem_object(base_);
-    base_ = nullptr;
-  }
-  explicit operator bool() const { return base_ != nullptr; }
-  bool owned() const { return base_ && owned_; }
-  dt_hip_mem_t base() const { return base_; }
-  size_t offset() const { return offset_; }
-  dt_hip_mem_t ptr() const { return base_ ? (dt_hip_mem_t)((char *)base_ + offset_) : nullptr; }
-};
 
 struct group_t
 {

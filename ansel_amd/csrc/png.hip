@@ -638,68 +638,55 @@ extern "C" int dt_hip_export_png(int devid, int width, int height, const dt_hip_
   const size_t sz_fs = (size_t)N, sz_m = level ? (size_t)N * 4 : 4, sz_tok = level ? (size_t)nseg * SEG_WORDS * 8 : 8;
   const size_t sz_freq = (size_t)nseg * NSYM * 4, sz_segs = (size_t)nseg * sizeof(pd_seg_t), sz_off = (size_t)nseg * 8;
   const size_t sz_words = (size_t)nwords * 4;
-  dt_hip_mem_t m_fs = dt_hip_alloc_device_buffer(devid, sz_fs);
-  dt_hip_mem_t m_m = dt_hip_alloc_device_buffer(devid, sz_m);
-  dt_hip_mem_t m_tok = dt_hip_alloc_device_buffer(devid, sz_tok);
-  dt_hip_mem_t m_mat = dt_hip_alloc_device_buffer(devid, sz_tok);
-  dt_hip_mem_t m_freq = dt_hip_alloc_device_buffer(devid, sz_freq);
-  dt_hip_mem_t m_segs = dt_hip_alloc_device_buffer(devid, sz_segs);
-  dt_hip_mem_t m_off = dt_hip_alloc_device_buffer(devid, sz_off);
-  dt_hip_mem_t m_words = dt_hip_alloc_device_buffer(devid, sz_words);
-  dt_hip_mem_t m_st = dt_hip_alloc_device_buffer(devid, sizeof(pstate_t));
-  dt_hip_mem_t m_head = dt_hip_alloc_device_buffer(devid, head.size());
-  auto release = [&]() {
-    for(dt_hip_mem_t x : { m_fs, m_m, m_tok, m_mat, m_freq, m_segs, m_off, m_words, m_st, m_head })
-      dt_hip_release_mem_object(x);
-  };
-  if(!m_fs || !m_m || !m_tok || !m_mat || !m_freq || !m_segs || !m_off || !m_words || !m_st || !m_head)
-  {
-    release();
-    return DT_HIP_DEFAULT_ERROR;
-  }
+  const dev_buf_t m_fs = dev_buf_t::alloc(devid, sz_fs);
+  const dev_buf_t m_m = dev_buf_t::alloc(devid, sz_m);
+  const dev_buf_t m_tok = dev_buf_t::alloc(devid, sz_tok);
+  const dev_buf_t m_mat = dev_buf_t::alloc(devid, sz_tok);
+  const dev_buf_t m_freq = dev_buf_t::alloc(devid, sz_freq);
+  const dev_buf_t m_segs = dev_buf_t::alloc(devid, sz_segs);
+  const dev_buf_t m_off = dev_buf_t::alloc(devid, sz_off);
+  const dev_buf_t m_words = dev_buf_t::alloc(devid, sz_words);
+  const dev_buf_t m_st = dev_buf_t::alloc(devid, sizeof(pstate_t));
+  const dev_buf_t m_head = dev_buf_t::alloc(devid, head.size());
+  if(!m_fs || !m_m || !m_tok || !m_mat || !m_freq || !m_segs || !m_off || !m_words || !m_st || !m_head) return DT_HIP_DEFAULT_ERROR;
   hipStream_t s = stream_of(devid);
-  int err = upload_small(devid, m_head, head.data(), head.size());
-  if(err != DT_HIP_SUCCESS)
-  {
-    release();
-    return err;
-  }
-  pd_seg_t *segs = (pd_seg_t *)m_segs;
-  pstate_t *st = (pstate_t *)m_st;
+  const int err = upload_small(devid, m_head.ptr(), head.data(), head.size());
+  if(err != DT_HIP_SUCCESS) return err;
+  pd_seg_t *segs = m_segs.as<pd_seg_t>();
+  pstate_t *st = m_st.as<pstate_t>();
   {
     launch_scope ls(devid, "png_filter");
-    png_filter<<<height, PT, 0, s>>>(dev_in, width, d->bit_depth, (uint8_t *)m_fs);
+    png_filter<<<height, PT, 0, s>>>(dev_in, width, d->bit_depth, m_fs.as<uint8_t>());
   }
   {
     launch_scope ls(devid, "png_lz");
-    png_lz<<<(unsigned)nseg, PT, 0, s>>>((const uint8_t *)m_fs, N, level, (uint32_t *)m_m, (uint64_t *)m_tok,
-                                         (uint64_t *)m_mat, (uint32_t *)m_freq, segs);
+    png_lz<<<(unsigned)nseg, PT, 0, s>>>(m_fs.as<const uint8_t>(), N, level, m_m.as<uint32_t>(), m_tok.as<uint64_t>(),
+                                         m_mat.as<uint64_t>(), m_freq.as<uint32_t>(), segs);
   }
   {
     launch_scope ls(devid, "png_tables");
-    png_tables<<<(unsigned)nseg, 64, 0, s>>>((const uint32_t *)m_freq, N, level, segs);
+    png_tables<<<(unsigned)nseg, 64, 0, s>>>(m_freq.as<const uint32_t>(), N, level, segs);
   }
   {
     launch_scope ls(devid, "png_scan");
-    png_scan<<<1, PT, 0, s>>>(segs, nseg, N, (uint32_t)head.size(), d->capacity, (uint64_t *)m_off, st,
+    png_scan<<<1, PT, 0, s>>>(segs, nseg, N, (uint32_t)head.size(), d->capacity, m_off.as<uint64_t>(), st,
                               (uint8_t *)dev_out);
   }
   {
     launch_scope ls(devid, "png_emit");
-    png_zero<<<stream_grid(nwords, PT), PT, 0, s>>>((uint32_t *)m_words, st);
-    png_emit<<<(unsigned)nseg, PT, 0, s>>>((const uint8_t *)m_fs, (const uint32_t *)m_m, (const uint64_t *)m_tok,
-                                           (const uint64_t *)m_mat, segs, (const uint64_t *)m_off, nseg,
-                                           (uint32_t *)m_words);
-    png_tail<<<1, 64, 0, s>>>((uint32_t *)m_words, pd_zlib_header(level), st);
+    png_zero<<<stream_grid(nwords, PT), PT, 0, s>>>(m_words.as<uint32_t>(), st);
+    png_emit<<<(unsigned)nseg, PT, 0, s>>>(m_fs.as<const uint8_t>(), m_m.as<const uint32_t>(), m_tok.as<const uint64_t>(),
+                                           m_mat.as<const uint64_t>(), segs, m_off.as<const uint64_t>(), nseg,
+                                           m_words.as<uint32_t>());
+    png_tail<<<1, 64, 0, s>>>(m_words.as<uint32_t>(), pd_zlib_header(level), st);
   }
   {
     launch_scope ls(devid, "png_idat");
-    png_idat<<<(unsigned)std::min<uint64_t>(max_idat, 2048), PT, 0, s>>>((const uint8_t *)m_words, st,
+    png_idat<<<(unsigned)std::min<uint64_t>(max_idat, 2048), PT, 0, s>>>(m_words.as<const uint8_t>(), st,
                                                                           (uint32_t)head.size(), crc_type,
                                                                           (uint8_t *)dev_out);
-    png_head<<<1, PT, 0, s>>>((const uint8_t *)m_head, (uint32_t)head.size(), st, (uint8_t *)dev_out);
+    png_head<<<1, PT, 0, s>>>(m_head.as<const uint8_t>(), (uint32_t)head.size(), st, (uint8_t *)dev_out);
   }
-  release();
   return check_launch("export_png");
 }
 
@@ -713,25 +700,23 @@ extern "C" int dt_hip_test_png_tables(int devid, const uint32_t *freq, uint64_t 
   if(!valid_device(devid) || !freq || !segs_out || nseg < 1 || nseg > 65536 || level < 0 || level > 9) return DT_HIP_INVALID_ARG;
   if(nbytes <= (uint64_t)(nseg - 1) * PD_SEG || nbytes > (uint64_t)nseg * PD_SEG) return DT_HIP_INVALID_ARG;
   const size_t sz_freq = (size_t)nseg * NSYM * 4, sz_segs = (size_t)nseg * sizeof(pd_seg_t);
-  dt_hip_mem_t m_freq = dt_hip_alloc_device_buffer(devid, sz_freq);
-  dt_hip_mem_t m_segs = dt_hip_alloc_device_buffer(devid, sz_segs);
+  const dev_buf_t m_freq = dev_buf_t::alloc(devid, sz_freq);
+  const dev_buf_t m_segs = dev_buf_t::alloc(devid, sz_segs);
   int err = (m_freq && m_segs) ? DT_HIP_SUCCESS : DT_HIP_DEFAULT_ERROR;
-  if(err == DT_HIP_SUCCESS) err = dt_hip_write_buffer_to_device(devid, freq, m_freq, 0, sz_freq, 1);
+  if(err == DT_HIP_SUCCESS) err = dt_hip_write_buffer_to_device(devid, freq, m_freq.ptr(), 0, sz_freq, 1);
   if(err == DT_HIP_SUCCESS)
   {
     hipStream_t s = stream_of(devid);
-    if(hipMemsetAsync(m_segs, 0, sz_segs, s) != hipSuccess) err = DT_HIP_DEFAULT_ERROR;
+    if(hipMemsetAsync(m_segs.ptr(), 0, sz_segs, s) != hipSuccess) err = DT_HIP_DEFAULT_ERROR;
   }
   if(err == DT_HIP_SUCCESS)
   {
     {
       launch_scope ls(devid, "png_tables");
-      png_tables<<<(unsigned)nseg, 64, 0, stream_of(devid)>>>((const uint32_t *)m_freq, nbytes, level, (pd_seg_t *)m_segs);
+      png_tables<<<(unsigned)nseg, 64, 0, stream_of(devid)>>>(m_freq.as<const uint32_t>(), nbytes, level, m_segs.as<pd_seg_t>());
     }
     err = check_launch("test_png_tables");
   }
-  if(err == DT_HIP_SUCCESS) err = dt_hip_read_buffer_from_device(devid, segs_out, m_segs, 0, sz_segs, 1);
-  if(m_freq) dt_hip_release_mem_object(m_freq);
-  if(m_segs) dt_hip_release_mem_object(m_segs);
+  if(err == DT_HIP_SUCCESS) err = dt_hip_read_buffer_from_device(devid, segs_out, m_segs.ptr(), 0, sz_segs, 1);
   return err;
 }

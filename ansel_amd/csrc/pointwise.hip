@@ -521,7 +521,9 @@ static int highlights_launch(int devid, const dt_hip_piece_t *piece, const dt_hi
   // _hl_count_thresholds(): clip mode tests the scalar clip on every channel (highlights.c:232-255)
   const float4 thr = make_float4(clip, clip, clip, clip);
   hipStream_t s = stream_of(devid);
-  hl_journal *journal = deferred ? (hl_journal *)deferred : (hl_journal *)dt_hip_alloc_device_buffer(devid, sizeof(hl_journal));
+  // the caller's (deferred: it resolves the journal later) or ours; stream-ordered: reused only by later work on this stream
+  const dev_buf_t journal_buf = deferred ? dev_buf_t::borrow(deferred) : dev_buf_t::alloc(devid, sizeof(hl_journal));
+  hl_journal *const journal = journal_buf.as<hl_journal>();
   if(!journal) return DT_HIP_SYSMEM_ALLOCATION;
   int err = DT_HIP_SUCCESS;
   if(hipMemsetAsync(journal, 0, sizeof(hl_journal), s) != hipSuccess) err = DT_HIP_DEFAULT_ERROR;
@@ -556,7 +558,6 @@ static int highlights_launch(int devid, const dt_hip_piece_t *piece, const dt_hi
       err = check_launch("highlights_clip_4f");
     }
   }
-  if(!deferred) dt_hip_release_mem_object(journal); // stream-ordered: reused only by later work on this stream
   return err;
 }
 

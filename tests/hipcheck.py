@@ -16,6 +16,13 @@ def hip():
     return _state["lib"]
 
 
+def allocated_bytes():
+    """what device 0 holds of the runtime's pool at this moment (lib.DeviceBuffer draws from the same pool)"""
+    cur, peak = C.c_size_t(0), C.c_size_t(0)
+    hip().dt_hip_memory_statistics(0, C.byref(cur), C.byref(peak))
+    return cur.value
+
+
 def run_hip(fn_name, piece, data, inp, out_shape, out_dtype=np.float32, pre_fill=None):
     """upload `inp`, call dt_hip_iop_<fn>_process(devid 0, piece, data, in, out), download"""
     h = hip()
@@ -26,9 +33,14 @@ def run_hip(fn_name, piece, data, inp, out_shape, out_dtype=np.float32, pre_fill
     else:
         dout = lib.DeviceBuffer.from_numpy(0, np.zeros(out_shape, dtype=out_dtype))
     fn = getattr(h, fn_name)
+    base = allocated_bytes()
     rc = fn(0, C.byref(piece), C.byref(data), din.ptr, dout.ptr)
+    finished = h.dt_hip_finish(0)
+    # whatever the module took from the runtime's pool is back in it, also where it refuses the call
+    left = allocated_bytes() - base
+    assert left == 0, "%s (rc %d) holds %d bytes of the pool after it returned" % (fn_name, rc, left)
     lib.check(rc, fn_name)
-    assert h.dt_hip_finish(0) == 1, h.dt_hip_last_error()
+    assert finished == 1, h.dt_hip_last_error()
     out = dout.to_numpy(out_shape, out_dtype)
     din.release()
     dout.release()

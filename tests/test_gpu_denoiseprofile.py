@@ -90,3 +90,43 @@ def test_variance_mode_is_refused():
     piece = abi.Piece.make(64, 64)
     d = params.denoiseprofile(mode=2)
     assert l.dt_hip_iop_denoiseprofile_process(0, C.byref(piece), C.byref(d), buf.ptr, buf.ptr) == abi.DT_HIP_INVALID_ARG
+
+
+def test_band_job_given_up_inside_the_wavelets_returns_its_planes():
+    """a row band of the 400 x 300 denoise pipe (two bands) walked as far as the wavelets' all-reduce stop -- every
+    decomposition done, so the band job holds its coarse plane, a detail plane per scale and the tables of sums -- and given
+    up there with dt_hip_pipe_band_abort(): the runtime's allocation counter is back at its baseline.  (The neighbour's halo
+    rows are not filled in: what the planes hold does not matter to who owns them.)"""
+    import ctypes as C
+    import torch
+    from ansel_amd import filmic, pipe, tiled
+    l = hc.hip()
+    w, h = 400, 300
+    lut = params.srgb_encode_lut()
+    d_lut = torch.from_numpy(lut).to("cuda:0")
+    nodes = pipe.denoise_pipe_nodes(w, h, d_lut.data_ptr(), float(lut[0]), params.unbounded_coeffs(lut),
+                                    filmic=filmic.default_data(), diffuse_iterations=2, with_nlmeans=True, with_bilat=True)
+    raw = torch.from_numpy(synth.bayer_mosaic(w, h, seed=2).view(np.int16)).to("cuda:0")
+    res = torch.zeros((h, w, 4), dtype=torch.int16, device="cuda:0")
+
+    def allocated():
+        torch.cuda.synchronize()
+        return hc.allocated_bytes()
+
+    base = allocated()
+    p = pipe.DevicePipe(0, nodes)
+    band = tiled.plan_bands(w, h, 2, tiled.pipe_demosaic_method(nodes))[0]
+    st = abi.BandState()
+    assert l.dt_hip_pipe_band_begin(p.handle, C.byref(band), raw.data_ptr(), C.byref(st)) == 0
+    assert l.dt_hip_pipe_band_resolve(p.handle, C.byref(band), C.byref(st)) == 0
+    for _ in range(16):  # the halo stop in front of the module, one per decomposition, then the sums
+        rc = l.dt_hip_pipe_band_finish(p.handle, C.byref(band), C.byref(st), res.data_ptr())
+        assert rc == abi.DT_HIP_BAND_EXCHANGE, (rc, l.dt_hip_last_error())
+        assert not st.relay_buf  # (the bilateral grid's relay comes behind the wavelets)
+        if st.sum_buf:
+            break
+    assert st.sum_buf and st.sum_planes > 0
+    assert allocated() > base
+    l.dt_hip_pipe_band_abort(p.handle, C.byref(st))
+    assert allocated() == base
+    p.close()

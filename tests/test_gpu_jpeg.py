@@ -44,9 +44,12 @@ def encode_dev(img, quality, subsampling, optimize, icc=None, density=(0, 1, 1),
     d_in = lib.DeviceBuffer.from_numpy(0, np.ascontiguousarray(img))
     out_init = np.full(d.capacity + GUARD, 0xA5, np.uint8)
     d_out = lib.DeviceBuffer.from_numpy(0, out_init)
+    held = hc.allocated_bytes()
     rc = l.dt_hip_export_jpeg(0, w, h, C.byref(d), d_in.ptr, d_out.ptr)
+    finished = l.dt_hip_finish(0)
+    assert hc.allocated_bytes() == held, "the encoder's scratch is not back in the pool (rc %d)" % rc
     assert rc == abi.DT_HIP_SUCCESS, hc.hip().dt_hip_last_error().decode()
-    assert l.dt_hip_finish(0) == 1
+    assert finished == 1
     buf = d_out.to_numpy((d.capacity + GUARD,), np.uint8)
     d_in.release()
     d_out.release()

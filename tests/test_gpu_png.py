@@ -36,9 +36,12 @@ def encode_dev(img, level, icc=None, dpi=None, capacity=None, raw=False):
     d.capacity = bound if capacity is None else capacity
     d_in = lib.DeviceBuffer.from_numpy(0, np.ascontiguousarray(img))
     d_out = lib.DeviceBuffer.from_numpy(0, np.full(d.capacity + GUARD, 0xA5, np.uint8))
+    held = hc.allocated_bytes()
     rc = l.dt_hip_export_png(0, w, h, C.byref(d), d_in.ptr, d_out.ptr)
+    finished = l.dt_hip_finish(0)
+    assert hc.allocated_bytes() == held, "the encoder's scratch is not back in the pool (rc %d)" % rc
     assert rc == abi.DT_HIP_SUCCESS, l.dt_hip_last_error().decode()
-    assert l.dt_hip_finish(0) == 1
+    assert finished == 1
     buf = d_out.to_numpy((d.capacity + GUARD,), np.uint8)
     d_in.release()
     d_out.release()
