@@ -265,6 +265,18 @@ class PngData(C.Structure):
                 ("capacity", C.c_uint64), ("icc", C.c_void_p), ("icc_bytes", C.c_uint64)]
 
 
+DT_HIP_TIFF_NONE = 1     # Compression tag 1
+DT_HIP_TIFF_DEFLATE = 8  # Compression tag 8 (Adobe deflate): one zlib stream per strip
+
+
+class TiffData(C.Structure):
+    """dt_hip_tiff_data_t: the TIFF encoder behind export_u8 / export_u16 / a float4 node (tiff.hip); icc is host memory
+    the call copies"""
+    _fields_ = [("bpp", C.c_int32), ("layers", C.c_int32), ("compression", C.c_int32), ("predictor", C.c_int32),
+                ("compression_level", C.c_int32), ("rows_per_strip", C.c_int32), ("dpi", C.c_int32),
+                ("capacity", C.c_uint64), ("icc", C.c_void_p), ("icc_bytes", C.c_uint64)]
+
+
 class Band(C.Structure):
     """dt_hip_band_t: a row band of a frame split over several devices"""
     _fields_ = [("row0", C.c_int32), ("rows", C.c_int32), ("halo_top", C.c_int32), ("halo_bottom", C.c_int32),

@@ -104,6 +104,8 @@ constexpr op_info_t k_ops[OP_UNKNOWN] = {
     run_encoder<dt_hip_jpeg_data_t, dt_hip_export_jpeg>, OPF_NO_PTP, no_band_mode },
   { OP_EXPORT_PNG, "export_png", sizeof(dt_hip_png_data_t), 0, encoder_capacity<dt_hip_png_data_t>,
     run_encoder<dt_hip_png_data_t, dt_hip_export_png>, OPF_NO_PTP, no_band_mode },
+  { OP_EXPORT_TIFF, "export_tiff", sizeof(dt_hip_tiff_data_t), 0, encoder_capacity<dt_hip_tiff_data_t>,
+    run_encoder<dt_hip_tiff_data_t, dt_hip_export_tiff>, OPF_NO_PTP, no_band_mode },
 };
 constexpr bool table_follows_enum()
 {
@@ -133,6 +135,7 @@ int make_node(node_t &n, const char *who, const char *name, const dt_hip_piece_t
   if(data_size) n.data.assign((const unsigned char *)data, (const unsigned char *)data + data_size);
   if(n.op == OP_EXPORT_JPEG) keep_icc<dt_hip_jpeg_data_t>(n);
   if(n.op == OP_EXPORT_PNG) keep_icc<dt_hip_png_data_t>(n);
+  if(n.op == OP_EXPORT_TIFF) keep_icc<dt_hip_tiff_data_t>(n);
   return DT_HIP_SUCCESS;
 }
 
@@ -178,6 +181,27 @@ void dt_hip_pipe_t::plan()
       {
         set_last_error("pipe: 'export_png' at %d bits must be the last node, directly behind '%s' (it is node %d of %d%s%s)", depth,
                        k_ops[want].name, k + 1, n, k ? ", behind " : "", k ? k_ops[nodes[k - 1].op].name : "");
+        placement.keep(DT_HIP_INVALID_ARG);
+      }
+    }
+  for(int k = 0; k < n && placement.code == DT_HIP_SUCCESS; k++)
+    if(nodes[k].op == OP_EXPORT_TIFF)
+    {
+      const int bpp = nodes[k].as<dt_hip_tiff_data_t>()->bpp;
+      // 8 / 16 bits: the export conversion of that depth; 32 bits: any node that writes four floats a pixel
+      const char *want = bpp == 8 ? "'export_u8'" : bpp == 16 ? "'export_u16'" : "a node that writes four floats a pixel";
+      bool ok = k + 1 == n && k > 0;
+      if(ok)
+      {
+        const node_t &p = nodes[k - 1];
+        const bool floats = p.op != OP_EXPORT_U8 && p.op != OP_EXPORT_U16 && p.op != OP_EXPORT_ROWS && p.op < OP_EXPORT_JPEG
+                            && (k_ops[p.op].bpp_out ? k_ops[p.op].bpp_out : 4 * (int)p.piece.channels) == 16;
+        ok = bpp == 8 ? p.op == OP_EXPORT_U8 : bpp == 16 ? p.op == OP_EXPORT_U16 : floats;
+      }
+      if(!ok)
+      {
+        set_last_error("pipe: 'export_tiff' at %d bits must be the last node, directly behind %s (it is node %d of %d%s%s)", bpp,
+                       want, k + 1, n, k ? ", behind " : "", k ? k_ops[nodes[k - 1].op].name : "");
         placement.keep(DT_HIP_INVALID_ARG);
       }
     }

@@ -155,6 +155,8 @@ def load():
         "dt_hip_export_jpeg": (i, [i, i, i, P(abi.JpegData), vp, vp]),
         "dt_hip_png_bound": (sz, [i, i, P(abi.PngData)]),
         "dt_hip_export_png": (i, [i, i, i, P(abi.PngData), vp, vp]),
+        "dt_hip_tiff_bound": (sz, [i, i, P(abi.TiffData)]),
+        "dt_hip_export_tiff": (i, [i, i, i, P(abi.TiffData), vp, vp]),
         "dt_hip_pipe_new": (vp, [i]),
         "dt_hip_pipe_free": (None, [vp]),
         "dt_hip_pipe_add_node": (i, [vp, C.c_char_p, P(abi.Piece), vp, sz]),

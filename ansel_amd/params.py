@@ -269,3 +269,33 @@ def png(bpp=8, compression=5, icc=None, dpi=None):
         d.icc = C.cast(d._icc, C.c_void_p)
         d.icc_bytes = len(icc)
     return d
+
+
+def tiff(bpp=8, compress=0, level=6, shortfile=False, icc=None, dpi=None):
+    """dt_hip_tiff_data_t for an Ansel TIFF export.  src/imageio/format/tiff.c was not at hand: the mapping of its dialog
+    is RECALLED, not read -- `bpp` 8, 16 or 32 (float); `compress` 0 none, 1 deflate, 2 deflate
+    with the predictor (horizontal at 8 / 16 bits, floating point at 32); `level` 0..9 the deflate level (dialog default
+    6); `shortfile`: one sample per pixel, MINISBLACK (the writer's grayscale mode).  Rows per strip: libtiff's default
+    rule.  icc: the output profile's bytes (tag 34675), kept alive by the returned struct.  dpi: None (no resolution
+    tags) or dots per inch.  `capacity` is left 0: set it to the output buffer's size (dt_hip_tiff_bound())."""
+    b, c, lv = int(bpp), int(compress), int(level)
+    if b not in (8, 16, 32):
+        raise ValueError("TIFF bpp %r: the device writes 8, 16 or 32 bits" % (bpp,))
+    if c not in (0, 1, 2):
+        raise ValueError("TIFF compress %r is not 0 (none), 1 (deflate) or 2 (deflate with predictor)" % (compress,))
+    if not 0 <= lv <= 9:
+        raise ValueError("TIFF level %r is outside 0..9" % (level,))
+    d = abi.TiffData(bpp=b, layers=1 if shortfile else 3,
+                     compression=abi.DT_HIP_TIFF_DEFLATE if c else abi.DT_HIP_TIFF_NONE,
+                     predictor=1 if c < 2 else 3 if b == 32 else 2, compression_level=lv, rows_per_strip=0, dpi=0)
+    if dpi is not None:
+        v = int(round(dpi))
+        if v <= 0:
+            raise ValueError("dpi %r is not positive" % (dpi,))
+        d.dpi = v
+    if icc:
+        icc = bytes(icc)
+        d._icc = C.create_string_buffer(icc, len(icc))
+        d.icc = C.cast(d._icc, C.c_void_p)
+        d.icc_bytes = len(icc)
+    return d

@@ -21,6 +21,7 @@ MODULE_BPP = {
     "flip": (16, 16),
     "export_u8": (16, 4), "export_jpeg": (4, 0),
     "export_png": (4, 0),  # 8 bits: node_bytes_per_px() reads 8 B/px at 16 bits
+    "export_tiff": (4, 0),  # 8 bits: node_bytes_per_px() reads 8 / 16 B/px at 16 / 32 bits
 }
 
 
@@ -84,6 +85,24 @@ def with_png(nodes, png_data):
 def png_bound(width, height, png_data):
     """dt_hip_png_bound(): a capacity the encoder's output always fits"""
     return int(lib.load().dt_hip_png_bound(width, height, C.byref(png_data)))
+
+
+def with_tiff(nodes, tiff_data):
+    """the node list with export_tiff appended (tiff_data: params.tiff() or an abi.TiffData, its capacity set --
+    tiff_bound()): at 16 bits behind the trailing export_u16, at 8 bits that node is swapped for export_u8 first, at 32
+    bits it is dropped and the encoder reads the float frame of the node in front of it.  The node's output is the
+    little-endian uint64 file length, then the file.  The other nodes are shared with `nodes`."""
+    if not nodes or nodes[-1].op != "export_u16":
+        raise ValueError("with_tiff: the node list does not end in export_u16")
+    last = nodes[-1]
+    w, h = last.piece.roi_out.width, last.piece.roi_out.height
+    head = {16: list(nodes), 8: list(nodes[:-1]) + [Node("export_u8", None, last.piece)], 32: list(nodes[:-1])}[int(tiff_data.bpp)]
+    return head + [Node("export_tiff", tiff_data, abi.Piece.make(w, h, channels=4))]
+
+
+def tiff_bound(width, height, tiff_data):
+    """dt_hip_tiff_bound(): a capacity the encoder's output always fits"""
+    return int(lib.load().dt_hip_tiff_bound(width, height, C.byref(tiff_data)))
 
 
 def light_pipe_nodes(width, height, lut_target_ptr, lut_first, lut_coeffs, with_filmic=True, filmic=None,
@@ -155,6 +174,8 @@ def node_bytes_per_px(n):
         return 96 * max(int(n.data.iterations), 1) * modinfo.diffuse_scales(n.piece, n.data)
     if n.op == "export_png":
         return int(n.data.bit_depth) // 2  # RGBA u8 or u16 in, the file (a fraction of it) out
+    if n.op == "export_tiff":
+        return int(n.data.bpp) // 2  # RGBA u8, u16 or f32 in, the file out
     return sum(MODULE_BPP[n.op])
 
 

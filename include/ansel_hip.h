@@ -491,6 +491,40 @@ size_t dt_hip_png_bound(int width, int height, const dt_hip_png_data_t *d); /* p
 int dt_hip_export_png(int devid, int width, int height, const dt_hip_png_data_t *d, dt_hip_mem_t dev_in,
                       dt_hip_mem_t dev_out);
 
+/* TIFF export on the device (ansel_amd/csrc/tiff.hip): a little-endian classic TIFF in strips, in libtiff's terms --
+ * `II*\0`, one IFD at offset 8 (tags ascending: 256 257 258 259 262 273 274 277 278 279 [282 283] 284 [296] [317] 339
+ * [34675]), the tag arrays, then the strips; every out-of-line value and every strip on an even offset.  Classic TIFF
+ * only: a file whose bound does not fit 32-bit offsets is refused, BigTIFF is not written.  dev_in: width x height RGBA
+ * u8 (bpp 8), RGBA u16 (bpp 16) or RGBA f32 (bpp 32); alpha is ignored.  A strip's payload is libtiff's byte for byte
+ * (predictor 2: per sample the difference from the pixel to the left, modulo 2^bpp; predictor 3: the row's floats as
+ * four big-endian byte planes, each byte the difference from the byte `layers` before it); with DT_HIP_TIFF_DEFLATE
+ * every strip is one zlib stream of its own (valid, not zlib's bytes; the deflate of png.hip restarted at every strip).
+ * dev_out receives a little-endian uint64 file length L, then the L bytes of the file.  If 8 + L exceeds `capacity` the
+ * length word is UINT64_MAX and nothing is written past `capacity`; the call does not wait for the device, so the caller
+ * reads the word.  dt_hip_tiff_bound(): a capacity that always suffices (0 for refused settings).  Refused with
+ * DT_HIP_INVALID_ARG: any field outside the values below, a predictor that does not belong to the bpp, a predictor
+ * other than 1 without deflate, width or height below 1, a bound beyond 32-bit offsets.  EXIF stays on the host.  In a
+ * pipe: node "export_tiff" (data dt_hip_tiff_data_t), the last node, directly behind "export_u8" (8 bits),
+ * "export_u16" (16 bits) or a node whose output is four floats a pixel (32 bits); its output is `capacity` bytes. */
+#define DT_HIP_TIFF_NONE 1    /* Compression tag 1 */
+#define DT_HIP_TIFF_DEFLATE 8 /* Compression tag 8 (Adobe deflate): one zlib stream per strip */
+typedef struct dt_hip_tiff_data_t
+{
+  int32_t bpp;               /* 8, 16 (unsigned), 32 (IEEE float) */
+  int32_t layers;            /* 3: RGB; 1: sample 0 of every pixel, MINISBLACK (as export_rows) */
+  int32_t compression;       /* DT_HIP_TIFF_* */
+  int32_t predictor;         /* 1 none; 2 horizontal (bpp 8/16 only); 3 floating point (bpp 32 only); deflate only */
+  int32_t compression_level; /* 0..9, same meaning as dt_hip_png_data_t */
+  int32_t rows_per_strip;    /* 0: libtiff's default rule, max(1, 8192 / row bytes); else >= 1 */
+  int32_t dpi;               /* 0: no resolution tags */
+  uint64_t capacity;         /* bytes of dev_out, the 8-byte length word included */
+  const void *icc;           /* host memory, may be NULL: tag 34675; copied by the call (and by dt_hip_pipe_add_node) */
+  uint64_t icc_bytes;
+} dt_hip_tiff_data_t;
+size_t dt_hip_tiff_bound(int width, int height, const dt_hip_tiff_data_t *d); /* pure, no device */
+int dt_hip_export_tiff(int devid, int width, int height, const dt_hip_tiff_data_t *d, dt_hip_mem_t dev_in,
+                       dt_hip_mem_t dev_out);
+
 /* diffuse or sharpen: process(), src/iop/diffuse.c:1155-1258 -> wavelets_process() (:978-1106),
  * decompose_2D_Bspline() (src/pixel/bspline.h:351-377), heat_PDE_diffusion() (diffuse.c:760-968).
  * The struct is dt_iop_diffuse_params_t (diffuse.c:76-105; commit_params memcpy's it, :133-138)
