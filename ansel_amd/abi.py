@@ -118,6 +118,10 @@ DT_HIP_DENOISEPROFILE_RGB = 0
 DT_HIP_DENOISEPROFILE_Y0U0V0 = 1
 
 
+DT_HIP_BILAT_BILATERAL = 0
+DT_HIP_BILAT_LOCAL_LAPLACIAN = 1
+
+
 class BilatData(C.Structure):
     """dt_hip_bilat_data_t == dt_iop_bilat_params_t (src/iop/bilat.c:78-86) + pipe->iscale"""
     _fields_ = [("mode", C.c_int), ("sigma_r", C.c_float), ("sigma_s", C.c_float), ("detail", C.c_float),

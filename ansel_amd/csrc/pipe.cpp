@@ -474,6 +474,9 @@ int dt_hip_pipe_process(dt_hip_pipe_t *pipe, dt_hip_mem_t dev_in, dt_hip_mem_t d
     }
     dev_buf_t out = pipe->is_final_group(gi) ? dev_buf_t::borrow(dev_out) : dev_buf_t::alloc(devid, out_bytes(last));
     if(!out) return DT_HIP_SYSMEM_ALLOCATION;
+    if(out.owned() && g.kind == group_t::SINGLE && pipe->leaves_unwritten_alpha(g.first)
+       && hipMemsetAsync(out.ptr(), 0, out_bytes(last), stream_of(devid)) != hipSuccess)
+      return DT_HIP_DEFAULT_ERROR;
     int err;
     if(g.kind == group_t::RAW)
       err = raw_group_launch(devid, g.raw, cur.ptr(), out.ptr());

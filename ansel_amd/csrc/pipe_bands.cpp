@@ -1137,6 +1137,14 @@ int dt_hip_pipe_band_finish(dt_hip_pipe_t *pipe, const dt_hip_band_t *band, dt_h
       err = DT_HIP_SYSMEM_ALLOCATION;
       break;
     }
+    // (of the two modules leaves_unwritten_alpha() names only the demosaic comes here: check_band_mode() refuses the local
+    // laplacian, bilat_band_supported(), so the stencil branches need no such clear)
+    if(out.owned() && g.kind == group_t::SINGLE && pipe->leaves_unwritten_alpha(g.first)
+       && hipMemsetAsync(out.base(), 0, bytes, stream_of(devid)) != hipSuccess)
+    {
+      err = DT_HIP_DEFAULT_ERROR;
+      break;
+    }
     if(first.op == OP_DEMOSAIC)
     {
       const dt_hip_demosaic_data_t *d = first.as<dt_hip_demosaic_data_t>();

@@ -89,6 +89,7 @@ dt_hip_batch_t *dt_hip_batch_new(dt_hip_pipe_t *pipe, int depth, size_t in_bytes
   b->submitted = 0;
   b->quit = false;
   b->s_up = b->s_down = nullptr;
+  if(!pipe->planned) pipe->plan();
   // streams and events belong to the device that is current when they are made: the pipe's, not whatever the
   // calling thread used last (hipEventRecord rejects an event of another device than its stream's)
   bool ok = make_current(pipe->devid) && hipStreamCreateWithFlags(&b->s_up, hipStreamNonBlocking) == hipSuccess
@@ -100,6 +101,9 @@ dt_hip_batch_t *dt_hip_batch_new(dt_hip_pipe_t *pipe, int depth, size_t in_bytes
     sl.d_out = dev_buf_t::alloc(pipe->devid, out_bytes);
     ok = sl.d_in && sl.d_out && hipEventCreateWithFlags(&sl.up, hipEventDisableTiming) == hipSuccess
          && hipEventCreate(&sl.kstart) == hipSuccess && hipEventCreate(&sl.done) == hipSuccess && hipEventCreate(&sl.down) == hipSuccess;
+    // a pipe that ends in a demosaic or the local laplacian leaves the fourth channel of its output to the buffer's owner, and
+    // that is the batch: cleared once, no frame writes those words (dt_hip_pipe_t::leaves_unwritten_alpha())
+    if(ok && pipe->output_keeps_the_callers_alpha()) ok = hipMemset(sl.d_out.ptr(), 0, out_bytes) == hipSuccess;
     b->slots.push_back(std::move(sl));
   }
   if(!ok)

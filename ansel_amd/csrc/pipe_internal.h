@@ -136,4 +136,32 @@ struct dt_hip_pipe_t
   bool is_blend_group(const size_t k) const { return k < groups.size() && nodes[groups[k].first].op == ansel::OP_BLEND; }
   // the group's output is the pipe's: it is the last group, or only the blend of its module follows
   bool is_final_group(const size_t k) const { return k + 1 == groups.size() || (is_blend_group(k + 1) && k + 2 == groups.size()); }
+  // The demosaics leave the fourth channel of their output to their caller, as the reference's do (RCD and PPG on the border
+  // ring, AMaZE and the passthroughs on the whole frame), and so does the local laplacian.  Where no node behind node k writes
+  // that channel whatever it finds (colorin, colorout, denoise (profiled)) or drops it (scanlines of three samples), the words
+  // reach the pipe's output -- and in a buffer of the executor's own they would be what the pool held: true then, and the walk
+  // clears the buffer before the module runs (a buffer of the caller's keeps what the caller put there).  The tests state the
+  // same rule for their node lists: tests/pipe_cases.py, SETS_ALPHA and alpha_is_written() -- change the two together
+  bool leaves_unwritten_alpha(const size_t k) const
+  {
+    const ansel::node_t &n = nodes[k];
+    const bool leaves = n.op == ansel::OP_DEMOSAIC
+                        || (n.op == ansel::OP_BILAT && n.as<dt_hip_bilat_data_t>()->mode == DT_HIP_BILAT_LOCAL_LAPLACIAN);
+    if(!leaves) return false;
+    for(size_t j = k + 1; j < nodes.size(); j++)
+    {
+      const ansel::op_t op = nodes[j].op;
+      if(op == ansel::OP_COLORIN || op == ansel::OP_COLOROUT || op == ansel::OP_DENOISEPROFILE) return false;
+      if(op == ansel::OP_EXPORT_ROWS && nodes[j].as<dt_hip_export_rows_t>()->layers == 3) return false;
+    }
+    return true;
+  }
+  // the same for the pipe's output: the group that writes it leaves the fourth channel to whoever owns that buffer (the batch
+  // owns its slots' and clears them once: pipe_batch.cpp)
+  bool output_keeps_the_callers_alpha() const
+  {
+    for(size_t k = 0; k < groups.size(); k++)
+      if(is_final_group(k)) return groups[k].kind == ansel::group_t::SINGLE && leaves_unwritten_alpha(groups[k].first);
+    return false;
+  }
 };

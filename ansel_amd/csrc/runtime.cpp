@@ -15,6 +15,7 @@
 #include "hip_common.h"
 
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <unordered_map>
 #include <map>
@@ -44,6 +45,8 @@ struct device_t
   std::vector<hipEvent_t> event_pool;
   size_t cur_bytes = 0, peak_bytes = 0;
   std::multimap<size_t, void *> free_pool;
+  // dt_hip_test_pool_fill(): bit 32 = on, the low word = the pattern every block handed out is filled with first
+  std::atomic<uint64_t> test_fill{ 0 };
   // upload_small(): a ring of pinned staging buffers, each with the event behind its last copy
   struct staging_t
   {
@@ -419,7 +422,7 @@ dt_hip_mem_t dt_hip_alloc_device_buffer(int devid, size_t size)
   if(!valid_device(devid) || size == 0) return nullptr;
   device_t *d = g_devs[devid];
   const size_t rounded = (size + 255) & ~(size_t)255;
-  std::lock_guard<std::mutex> g(g_mutex);
+  std::unique_lock<std::mutex> g(g_mutex);
   void *p = nullptr;
   auto it = d->free_pool.find(rounded);
   if(it != d->free_pool.end())
@@ -450,7 +453,33 @@ dt_hip_mem_t dt_hip_alloc_device_buffer(int devid, size_t size)
   g_allocs[p] = { rounded, devid, 0, 0, 0, nullptr };
   d->cur_bytes += rounded;
   if(d->cur_bytes > d->peak_bytes) d->peak_bytes = d->cur_bytes;
+  g.unlock();
+  const uint64_t fill = d->test_fill.load(std::memory_order_relaxed);
+  if(fill >> 32)
+  {
+    // the tests' poison: the whole rounded block, pooled or fresh.  The drain keeps the fill ahead of whatever the caller
+    // does with the block on ANOTHER stream (the batch's upload stream); it exists in this mode only
+    make_current(devid);
+    if(hipMemsetD32Async((hipDeviceptr_t)p, (int)(uint32_t)fill, rounded / 4, d->stream) != hipSuccess
+       || hipStreamSynchronize(d->stream) != hipSuccess)
+    {
+      set_last_error("dt_hip_alloc_device_buffer: the test fill of %zu bytes failed", rounded);
+      (void)hipGetLastError();
+      dt_hip_release_mem_object(p);
+      return nullptr;
+    }
+  }
   return p;
+}
+
+// For the tests only (not in include/ansel_hip.h): while enabled, every block dt_hip_alloc_device_buffer() hands out -- from
+// the pool or fresh -- holds `pattern` in each of its 32-bit words, so that a kernel which reads scratch it has not written
+// reads poison and not the previous call's values.  Returns the previous enable state, -1 for an invalid device.
+int dt_hip_test_pool_fill(int devid, int enable, uint32_t pattern)
+{
+  if(!valid_device(devid)) return -1;
+  const uint64_t next = enable ? (((uint64_t)1 << 32) | pattern) : 0;
+  return (int)(g_devs[devid]->test_fill.exchange(next, std::memory_order_relaxed) >> 32);
 }
 
 dt_hip_mem_t dt_hip_alloc_device(int devid, int width, int height, int bpp)

@@ -12,6 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ANSEL_HIP_LIB") or os.path.join(HERE, "libansel_hip.so")
 
 _lib = None
+_env_fill = False  # env_pool_fill(): not read yet
+_env_fill_applied = False  # init() switches the fill on once
 
 
 class AnselHipError(RuntimeError):
@@ -183,6 +185,7 @@ def load():
         "dt_hip_iop_highlights_resolve": (i, [i, vp, vp]),
         "dt_hip_test_dispatch": (i, [C.c_char_p, i]),
         "dt_hip_test_nlm_last": (i, [P(i)]),
+        "dt_hip_test_pool_fill": (i, [i, i, u]),
     }
     missing = []
     for name, (res, args) in protos.items():
@@ -203,6 +206,16 @@ def test_dispatch(key, value):
     """dt_hip_test_dispatch() (csrc/testhooks.hip): send launches to a fallback kernel the library carries anyway -- "nlm_v2",
     "nlm_fused", "amaze_unfused", "amaze_slab", "amaze_blocks" -- on frames where the primary kernel applies; 0 clears"""
     check(load().dt_hip_test_dispatch(key.encode(), int(value)), "dt_hip_test_dispatch(%s)" % key)
+
+
+def test_pool_fill(devid, enable, pattern=0):
+    """dt_hip_test_pool_fill() (csrc/runtime.cpp): while enabled, every block dt_hip_alloc_device_buffer() hands out on `devid`,
+    pooled or fresh, is filled with the 32-bit `pattern` first -- scratch a kernel reads without having written it then holds
+    poison and not the previous call's values.  -> the previous enable state"""
+    was = load().dt_hip_test_pool_fill(devid, 1 if enable else 0, int(pattern) & 0xFFFFFFFF)
+    if was < 0:
+        raise AnselHipError("dt_hip_test_pool_fill: no device %d" % devid)
+    return bool(was)
 
 
 NLM_BODIES = ("none", "tall", "v4", "v3", "v2", "pipelined", "staged", "global")
@@ -231,7 +244,23 @@ def init():
         raise AnselHipError("libansel_hip.so lacks symbols declared in include/ansel_hip.h: %s"
                             % ", ".join(lib._ansel_missing))
     check(lib.dt_hip_init(), "dt_hip_init")
+    # a pass of the tests under poison (tests/hipcheck.py keeps the state from here on): also for a test that never calls hc.hip()
+    global _env_fill_applied
+    if not _env_fill_applied:
+        _env_fill_applied = True
+        if env_pool_fill() is not None:
+            test_pool_fill(0, True, env_pool_fill())
     return lib
+
+
+def env_pool_fill():
+    """ANSEL_TEST_POOL_FILL=<hex>, read once: the 32-bit word a whole test process runs its pool under, or None (the one
+    place the variable is parsed; tests/hipcheck.py takes the value from here)"""
+    global _env_fill
+    if _env_fill is False:
+        env = os.environ.get("ANSEL_TEST_POOL_FILL")
+        _env_fill = (int(env, 16) & 0xFFFFFFFF) if env else None
+    return _env_fill
 
 
 class DeviceBuffer:

@@ -1,5 +1,6 @@
 """Shared helpers for the -m gpu parity tests: run a module through the C-ABI of libansel_hip
 on device 0 and through the CPU checkers (tests/checkers.py) on the same seeded input."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -13,7 +14,32 @@ _state = {}
 def hip():
     if "lib" not in _state:
         _state["lib"] = lib.init()  # raises loudly when the .so or the GPU is missing
+        pool_fill_default()
     return _state["lib"]
+
+
+def pool_fill_default():
+    """the allocator's poison as the process runs: off, or -- ANSEL_TEST_POOL_FILL=<hex>, read once -- on with that word for
+    every test of the process (a one-time pass of the whole suite under poison; lib.init() switches it on from the same
+    variable, so a test file that never comes through hip() runs under it as well)"""
+    _state["fill"] = lib.env_pool_fill()
+    lib.test_pool_fill(0, _state["fill"] is not None, _state["fill"] or 0)
+
+
+@contextlib.contextmanager
+def pool_fill(pattern):
+    """every block the runtime's pool hands out inside the `with` holds the 32-bit `pattern` in each word (the modules'
+    scratch and lib.DeviceBuffer alike); what held before -- off, or an outer pattern -- is back afterwards"""
+    hip()
+    before = _state.get("fill")
+    was_on = lib.test_pool_fill(0, True, pattern)
+    assert was_on == (before is not None)
+    _state["fill"] = int(pattern) & 0xFFFFFFFF
+    try:
+        yield
+    finally:
+        _state["fill"] = before
+        lib.test_pool_fill(0, before is not None, before or 0)
 
 
 def allocated_bytes():
@@ -47,12 +73,13 @@ def run_hip(fn_name, piece, data, inp, out_shape, out_dtype=np.float32, pre_fill
     return out
 
 
-def run_cpu(which, name, piece, data, inp, out_shape, out_dtype=np.float32):
-    """which: 'ref' (the reference's own code, oracle/_ref) or 'oracle' (restatement)"""
+def run_cpu(which, name, piece, data, inp, out_shape, out_dtype=np.float32, pre_fill=None):
+    """which: 'ref' (the reference's own code, oracle/_ref) or 'oracle' (restatement); pre_fill: what the output holds
+    before the call, as in run_hip() (default: zeros)"""
     l = ck.ref() if which == "ref" else ck.oracle()
     if l is None:
         return None
-    out = np.zeros(out_shape, dtype=out_dtype)
+    out = np.zeros(out_shape, dtype=out_dtype) if pre_fill is None else np.array(pre_fill, dtype=out_dtype, order="C")
     rc = ck.call(l, ("ref_" if which == "ref" else "oracle_") + name, piece, data, np.ascontiguousarray(inp), out)
     assert rc == 0
     return out

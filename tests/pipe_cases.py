@@ -273,7 +273,11 @@ def device_modulewise(nodes, src):
                 prev = None
                 continue
             shape, dtype = _node_out(n)
-            out = lib.DeviceBuffer(0, int(np.prod(shape)) * np.dtype(dtype).itemsize)
+            if n.op == "demosaic" or (n.op == "bilat" and n.data.mode == abi.DT_HIP_BILAT_LOCAL_LAPLACIAN):
+                # the fourth channel these two leave alone is the caller's: zeros, as oracle_chain(fill=0.0) has them
+                out = lib.DeviceBuffer.from_numpy(0, np.zeros(shape, dtype))
+            else:  # every word is the module's to write: whatever the pool holds (poison under hc.pool_fill())
+                out = lib.DeviceBuffer(0, int(np.prod(shape)) * np.dtype(dtype).itemsize)
             bufs.append(out)
             if n.op == "export_u8":
                 lib.check(l.dt_hip_export_convert_u8(0, w, h, cur.ptr, out.ptr), n.op)
@@ -892,7 +896,8 @@ SCALED_SEEDS = tuple(range(1, 25))
 # The demosaic leaves the fourth channel to its caller, as the reference does: RCD on its border ring, AMaZE on the whole frame
 # (rcd.c:96-127, amaze.cc); the local laplacian leaves it alone too.  The resampler, the Lab conversions, exposure,
 # channelmixerrgb, filmic v4, diffuse and the bilateral grid carry or filter what they find there, and non-local means gives NaN
-# for NaN.  These write a value of their own whatever they find:
+# for NaN.  These write a value of their own whatever they find (the executor holds the same rule for the buffers it owns,
+# dt_hip_pipe_t::leaves_unwritten_alpha() in csrc/pipe_internal.h: change the two together):
 SETS_ALPHA = ("colorin", "colorout", "denoiseprofile")
 
 
@@ -902,7 +907,7 @@ def alpha_is_written(nodes):
     the host and on the device (tests/test_pipe_cases.py holds the scaled lists to this with the oracle's buffers full of NaN)"""
     written = True
     for n in nodes:
-        if n.op == "demosaic" or (n.op == "bilat" and n.data.mode != 0):
+        if n.op == "demosaic" or (n.op == "bilat" and n.data.mode == abi.DT_HIP_BILAT_LOCAL_LAPLACIAN):
             written = False
         elif n.op in SETS_ALPHA or (n.op == "export_rows" and n.data.layers == 3):
             written = True

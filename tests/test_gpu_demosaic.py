@@ -31,26 +31,32 @@ def _stale_mask(w, h, filters):
 RCD_SIZES = [(112, 112), (100, 90), (300, 200), (207, 131), (512, 384), (1502, 1002), (2000, 1300)]
 
 
-@pytest.mark.parametrize("w,h", RCD_SIZES)
-@pytest.mark.parametrize("roi_xy", [(0, 0), (1, 0), (0, 1), (1, 1)])
-def test_rcd(w, h, roi_xy):
-    if roi_xy != (0, 0) and (w, h) not in [(300, 200), (512, 384)]:
-        pytest.skip("CFA phase variants on two sizes only")
+def check_rcd(w, h, roi_xy, out_fill=None):
+    """out_fill: the 32-bit word the output holds before the call, on the device and in both checkers (default: zeros)"""
     img = _normalised_cfa(w, h)
+    pre = None if out_fill is None else np.full((h, w, 4), out_fill, np.uint32).view(np.float32)
     pm = synth.WB_COEFFS
     piece = abi.Piece.make(w, h, filters=synth.FILTERS_RGGB, channels=1, processed_maximum=pm,
                            roi_in=abi.Roi.make(*roi_xy, w, h), roi_out=abi.Roi.make(*roi_xy, w, h))
     d = abi.DemosaicData(0, 0, abi.DT_HIP_DEMOSAIC_RCD, 0.0)
-    got = hc.run_hip("dt_hip_iop_demosaic_process", piece, d, img, (h, w, 4))
-    exp = hc.run_cpu("oracle", "demosaic", piece, d, img, (h, w, 4))
+    got = hc.run_hip("dt_hip_iop_demosaic_process", piece, d, img, (h, w, 4), pre_fill=pre)
+    exp = hc.run_cpu("oracle", "demosaic", piece, d, img, (h, w, 4), pre_fill=pre)
     hc.assert_bit_exact(got, exp, "rcd vs oracle")
-    ref = hc.run_cpu("ref", "demosaic", piece, d, img, (h, w, 4))
+    ref = hc.run_cpu("ref", "demosaic", piece, d, img, (h, w, 4), pre_fill=pre)
     if ref is not None:
         # the reference reads stale per-thread scratch on <= 3 columns of a partial last tile
         # column (oracle/src/demosaic_rcd.c header); everywhere else it must agree exactly
         filters = hc.hip().dt_hip_crop_dcraw_filters(synth.FILTERS_RGGB, roi_xy[0], roi_xy[1])
         mask = _stale_mask(w, h, filters)
         hc.assert_bit_exact(got, ref, "rcd vs reference", mask=mask[..., None])
+
+
+@pytest.mark.parametrize("w,h", RCD_SIZES)
+@pytest.mark.parametrize("roi_xy", [(0, 0), (1, 0), (0, 1), (1, 1)])
+def test_rcd(w, h, roi_xy):
+    if roi_xy != (0, 0) and (w, h) not in [(300, 200), (512, 384)]:
+        pytest.skip("CFA phase variants on two sizes only")
+    check_rcd(w, h, roi_xy)
 
 
 @pytest.mark.parametrize("w,h", [(300, 200), (1502, 1002), (65, 40)])
