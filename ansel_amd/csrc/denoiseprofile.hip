@@ -771,8 +771,7 @@ static void launch_decompose(hipStream_t st, const float4 *in, float4 *coarse, f
   }
 #endif
   const int classes = height < mult ? height : mult, per_class = (height + mult - 1) / mult;
-  int strip = 32;
-  while(strip > 4 && (size_t)nseg * classes * ((per_class + strip - 1) / strip) < 2048) strip /= 2;
+  const int strip = strip_rows(nseg, classes, per_class);
   const int strips_per_class = (per_class + strip - 1) / strip;
   const dim3 grid(nseg, classes * strips_per_class);
   // (an ALPHA0 launch keeps three floats a sample: DN_LDS())

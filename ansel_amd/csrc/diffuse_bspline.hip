@@ -489,8 +489,7 @@ int bspline_launch_decompose2(int devid, hipStream_t s, const float4 *in, float4
   const int classes = h < m2 ? h : m2, per_class = (h + m2 - 1) / m2;
   const int gx = (w + 255) / 256;
   // four rows of low1 a strip are formed twice (its neighbours' too): long strips
-  int strip = 64;
-  while(strip > 4 && (size_t)gx * classes * ((per_class + strip - 1) / strip) < 2048) strip /= 2;
+  const int strip = strip_rows(gx, classes, per_class, 64);
   const int spc = (per_class + strip - 1) / strip;
   const dim3 grid(gx, classes * spc);
   launch_scope ls(devid, "diffuse_decompose");
@@ -527,8 +526,7 @@ int bspline_launch_decompose3(int devid, hipStream_t s, const void *in, bool in4
   if(in4 && mult != 1) return DT_HIP_INVALID_ARG;
   const int classes = h < mult ? h : mult, per_class = (h + mult - 1) / mult;
   const int gx = (w + 255) / 256; // a workgroup a span of 256 columns
-  int strip = 32;
-  while(strip > 4 && (size_t)gx * classes * ((per_class + strip - 1) / strip) < 2048) strip /= 2;
+  const int strip = strip_rows(gx, classes, per_class);
   const int spc = (per_class + strip - 1) / strip;
   const dim3 grid(gx, classes * spc);
   launch_scope ls(devid, "diffuse_decompose");
@@ -569,8 +567,7 @@ int bspline_launch_decompose(int devid, hipStream_t s, const float4 *in, float4 
 #endif
   const int classes = h < mult ? h : mult, per_class = (h + mult - 1) / mult;
   const int gx = mult == 1 ? (steps + 255) / 256 : (mult == 2 ? (steps + 127) / 128 : (mult == 4 ? (steps + 63) / 64 : ((steps + 31) / 32) * (mult / 8)));
-  int strip = 32;
-  while(strip > 4 && (size_t)gx * classes * ((per_class + strip - 1) / strip) < 2048) strip /= 2;
+  const int strip = strip_rows(gx, classes, per_class);
   const int spc = (per_class + strip - 1) / strip;
   const dim3 grid(gx, classes * spc);
   if(mult == 1) bspline_decompose_strip<1, 256><<<grid, 256, 0, s>>>(in, hf, lf, w, h, mult, 1, strip, spc, gate);

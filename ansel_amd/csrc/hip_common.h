@@ -35,9 +35,23 @@ enum dispatch_key_t
   DISPATCH_AMAZE_SLAB,      // AMaZE: every tile on the first kernel
   DISPATCH_AMAZE_BLOCKS,    // AMaZE: at most this many workgroups (a workgroup then walks many tiles)
   DISPATCH_BILAT_BLUR_SPLIT, // bilateral grid: the blur's x-pass in a launch of its own (what grids beyond 2^22 cells take)
+  DISPATCH_STRIP_ROWS,      // the strip kernels (strip_rows()): 4, 8, 16 or 32 rows a strip at every site, whatever the frame
   DISPATCH_KEYS
 };
 int dispatch_override(dispatch_key_t key); // 0: not set
+
+// Rows a workgroup of a strip kernel keeps its 256 columns for (dn_decompose_strip, diffuse_pde_strip / _strip3,
+// bspline_decompose_strip / _strip3): gx column spans, `classes` dilation classes of per_class rows each.  The longest
+// strip that still leaves 2048 workgroups, and 4 rows at the least: 32 from about 16.8 MP on, 4 on the frames of the module
+// tests -- which is why the tests can force the length (DISPATCH_STRIP_ROWS, tests/test_gpu_strip_rows.py)
+static inline int strip_rows(const int gx, const int classes, const int per_class, const int longest = 32)
+{
+  const int forced = dispatch_override(DISPATCH_STRIP_ROWS);
+  if(forced) return forced;
+  int strip = longest;
+  while(strip > 4 && (size_t)gx * classes * ((per_class + strip - 1) / strip) < 2048) strip /= 2;
+  return strip;
+}
 
 void set_last_error(const char *fmt, ...);
 

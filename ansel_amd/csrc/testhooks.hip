@@ -13,7 +13,7 @@ namespace
 {
 std::atomic<int> g_dispatch[DISPATCH_KEYS];
 const char *const g_dispatch_names[DISPATCH_KEYS] = { "nlm_v2", "nlm_fused", "amaze_unfused", "amaze_slab", "amaze_blocks",
-                                                       "bilat_blur_split" };
+                                                       "bilat_blur_split", "strip_rows" };
 } // namespace
 namespace ansel
 {
@@ -25,11 +25,16 @@ extern "C" int dt_hip_test_dispatch(const char *key, int value)
   for(int k = 0; k < DISPATCH_KEYS; k++)
     if(!strcmp(key, g_dispatch_names[k]))
     {
+      // a strip length the kernels are not launched with anywhere is no test of them
+      if(k == DISPATCH_STRIP_ROWS && value != 0 && value != 4 && value != 8 && value != 16 && value != 32) return DT_HIP_INVALID_ARG;
       g_dispatch[k].store(value);
       return DT_HIP_SUCCESS;
     }
   return DT_HIP_INVALID_ARG;
 }
+
+// what the strip kernels' launch sites use now (hip_common.h strip_rows(), "strip_rows" included); touches no device
+extern "C" int dt_hip_test_strip_rows(int gx, int classes, int per_class) { return strip_rows(gx, classes, per_class); }
 
 // ---- test hooks: the device build of devmath.h on plain arrays (tests/test_gpu_devmath.py) ----
 namespace

@@ -184,6 +184,7 @@ def load():
         "dt_hip_iop_highlights_process_deferred": (i, [i, P(abi.Piece), P(abi.HighlightsData), vp, vp, vp]),
         "dt_hip_iop_highlights_resolve": (i, [i, vp, vp]),
         "dt_hip_test_dispatch": (i, [C.c_char_p, i]),
+        "dt_hip_test_strip_rows": (i, [i, i, i]),
         "dt_hip_test_nlm_last": (i, [P(i)]),
         "dt_hip_test_pool_fill": (i, [i, i, u]),
     }
@@ -204,8 +205,15 @@ def load():
 
 def test_dispatch(key, value):
     """dt_hip_test_dispatch() (csrc/testhooks.hip): send launches to a fallback kernel the library carries anyway -- "nlm_v2",
-    "nlm_fused", "amaze_unfused", "amaze_slab", "amaze_blocks" -- on frames where the primary kernel applies; 0 clears"""
+    "nlm_fused", "amaze_unfused", "amaze_slab", "amaze_blocks" -- on frames where the primary kernel applies, or the strip
+    kernels to a strip length larger frames take ("strip_rows": 4, 8, 16 or 32); 0 clears"""
     check(load().dt_hip_test_dispatch(key.encode(), int(value)), "dt_hip_test_dispatch(%s)" % key)
+
+
+def test_strip_rows(gx, classes, per_class):
+    """dt_hip_test_strip_rows() (csrc/testhooks.hip): rows a strip at the strip kernels' launch sites for gx column spans and
+    `classes` dilation classes of per_class rows, a "strip_rows" override included; no device needed"""
+    return load().dt_hip_test_strip_rows(int(gx), int(classes), int(per_class))
 
 
 def test_pool_fill(devid, enable, pattern=0):
