@@ -281,6 +281,13 @@ class TiffData(C.Structure):
                 ("capacity", C.c_uint64), ("icc", C.c_void_p), ("icc_bytes", C.c_uint64)]
 
 
+class WebpData(C.Structure):
+    """dt_hip_webp_data_t: the lossless WebP (VP8L) encoder behind export_u8 (webp.hip); icc is host memory the call
+    copies"""
+    _fields_ = [("lossless", C.c_int32), ("level", C.c_int32), ("predictor_bits", C.c_int32), ("entropy_bits", C.c_int32),
+                ("capacity", C.c_uint64), ("icc", C.c_void_p), ("icc_bytes", C.c_uint64)]
+
+
 class Band(C.Structure):
     """dt_hip_band_t: a row band of a frame split over several devices"""
     _fields_ = [("row0", C.c_int32), ("rows", C.c_int32), ("halo_top", C.c_int32), ("halo_bottom", C.c_int32),

@@ -12,12 +12,14 @@
 //
 // jh_build() is that body with the alphabet, the length limit and the reserved pseudo-symbol as arguments: the PNG
 // encoder's deflate (png_deflate.h) builds its 286 / 30 / 19-symbol codes with it, limited to 15 / 15 / 7 bits and
-// without the pseudo-symbol, so that each code is complete as inflate requires (the K.3 moves keep the Kraft sum).
+// without the pseudo-symbol, so that each code is complete as inflate requires (the K.3 moves keep the Kraft sum).  The
+// WebP encoder (webp_body.h) builds its 280 / 256 / 40 / 19-symbol codes with it too, and calls it on the host of a HIP
+// translation unit for the fixed codes of its sub-images: under hipcc the functions are __host__ __device__.
 #pragma once
 #include <stdint.h>
 
 #ifdef __HIPCC__
-#define JH_FN __device__ __forceinline__
+#define JH_FN __host__ __device__ __forceinline__
 #else
 #define JH_FN inline
 #endif

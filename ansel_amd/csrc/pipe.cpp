@@ -106,6 +106,8 @@ constexpr op_info_t k_ops[OP_UNKNOWN] = {
     run_encoder<dt_hip_png_data_t, dt_hip_export_png>, OPF_NO_PTP, no_band_mode },
   { OP_EXPORT_TIFF, "export_tiff", sizeof(dt_hip_tiff_data_t), 0, encoder_capacity<dt_hip_tiff_data_t>,
     run_encoder<dt_hip_tiff_data_t, dt_hip_export_tiff>, OPF_NO_PTP, no_band_mode },
+  { OP_EXPORT_WEBP, "export_webp", sizeof(dt_hip_webp_data_t), 0, encoder_capacity<dt_hip_webp_data_t>,
+    run_encoder<dt_hip_webp_data_t, dt_hip_export_webp>, OPF_NO_PTP, no_band_mode },
 };
 constexpr bool table_follows_enum()
 {
@@ -136,6 +138,7 @@ int make_node(node_t &n, const char *who, const char *name, const dt_hip_piece_t
   if(n.op == OP_EXPORT_JPEG) keep_icc<dt_hip_jpeg_data_t>(n);
   if(n.op == OP_EXPORT_PNG) keep_icc<dt_hip_png_data_t>(n);
   if(n.op == OP_EXPORT_TIFF) keep_icc<dt_hip_tiff_data_t>(n);
+  if(n.op == OP_EXPORT_WEBP) keep_icc<dt_hip_webp_data_t>(n);
   return DT_HIP_SUCCESS;
 }
 
@@ -169,6 +172,13 @@ void dt_hip_pipe_t::plan()
     if(nodes[k].op == OP_EXPORT_JPEG && (k + 1 != n || k == 0 || nodes[k - 1].op != OP_EXPORT_U8))
     {
       set_last_error("pipe: 'export_jpeg' must be the last node, directly behind 'export_u8' (it is node %d of %d%s%s)", k + 1, n,
+                     k ? ", behind " : "", k ? k_ops[nodes[k - 1].op].name : "");
+      placement.keep(DT_HIP_INVALID_ARG);
+    }
+  for(int k = 0; k < n && placement.code == DT_HIP_SUCCESS; k++)
+    if(nodes[k].op == OP_EXPORT_WEBP && (k + 1 != n || k == 0 || nodes[k - 1].op != OP_EXPORT_U8))
+    {
+      set_last_error("pipe: 'export_webp' must be the last node, directly behind 'export_u8' (it is node %d of %d%s%s)", k + 1, n,
                      k ? ", behind " : "", k ? k_ops[nodes[k - 1].op].name : "");
       placement.keep(DT_HIP_INVALID_ARG);
     }

@@ -163,7 +163,7 @@ static void check_band_mode(dt_hip_pipe_t *pipe)
   auto refuse = [&]() { pipe->band_mode.keep(DT_HIP_INVALID_ARG); };
   const int W = pipe->nodes[0].piece.roi_out.width, H = pipe->nodes[0].piece.roi_out.height;
   for(const node_t &n : pipe->nodes)
-    if(n.op == OP_EXPORT_JPEG || n.op == OP_EXPORT_PNG || n.op == OP_EXPORT_TIFF)
+    if(n.op == OP_EXPORT_JPEG || n.op == OP_EXPORT_PNG || n.op == OP_EXPORT_TIFF || n.op == OP_EXPORT_WEBP)
     {
       // a file is not rows: the entropy-coded data (the zlib stream) of one band depends on every band before it
       set_last_error("band mode: '%s' encodes the whole frame and has no row-band implementation", k_ops[n.op].name);

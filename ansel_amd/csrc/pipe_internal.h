@@ -44,6 +44,7 @@ enum op_t
   OP_EXPORT_JPEG, // the last node, behind export_u8: a file, not pixels
   OP_EXPORT_PNG,  // the last node, behind export_u8 (8 bits) or export_u16 (16 bits): a file
   OP_EXPORT_TIFF, // the last node, behind export_u8, export_u16 or (32 bits) a node that writes four floats a pixel: a file
+  OP_EXPORT_WEBP, // the last node, behind export_u8: a file, not a frame
   OP_UNKNOWN
 };
 static_assert(OP_COLORIN == OP_EXPOSURE + 1 && OP_CHANNELMIXERRGB == OP_EXPOSURE + 2 && OP_FILMICRGB == OP_EXPOSURE + 3
@@ -55,7 +56,7 @@ struct node_t
   op_t op;
   dt_hip_piece_t piece;
   std::vector<unsigned char> data;
-  std::vector<unsigned char> icc; // export_jpeg / export_png / export_tiff: the node's copy of the ICC profile its data pointed to
+  std::vector<unsigned char> icc; // export_jpeg / export_png / export_tiff / export_webp: the node's copy of the ICC profile its data pointed to
   template <typename T> const T *as() const { return reinterpret_cast<const T *>(data.data()); }
 };
 

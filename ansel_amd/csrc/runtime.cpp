@@ -942,6 +942,7 @@ size_t dt_hip_abi_sizeof(const char *name)
   S("jpeg", dt_hip_jpeg_data_t);
   S("png", dt_hip_png_data_t);
   S("tiff", dt_hip_tiff_data_t);
+  S("webp", dt_hip_webp_data_t);
   S("tile_plan", dt_hip_tile_plan_t);
   S("band", dt_hip_band_t);
   S("band_state", dt_hip_band_state_t);

@@ -159,6 +159,8 @@ def load():
         "dt_hip_export_png": (i, [i, i, i, P(abi.PngData), vp, vp]),
         "dt_hip_tiff_bound": (sz, [i, i, P(abi.TiffData)]),
         "dt_hip_export_tiff": (i, [i, i, i, P(abi.TiffData), vp, vp]),
+        "dt_hip_webp_bound": (sz, [i, i, P(abi.WebpData)]),
+        "dt_hip_export_webp": (i, [i, i, i, P(abi.WebpData), vp, vp]),
         "dt_hip_pipe_new": (vp, [i]),
         "dt_hip_pipe_free": (None, [vp]),
         "dt_hip_pipe_add_node": (i, [vp, C.c_char_p, P(abi.Piece), vp, sz]),

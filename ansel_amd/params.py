@@ -299,3 +299,32 @@ def tiff(bpp=8, compress=0, level=6, shortfile=False, icc=None, dpi=None):
         d.icc = C.cast(d._icc, C.c_void_p)
         d.icc_bytes = len(icc)
     return d
+
+
+def webp(comp_type=1, quality=95, hint=0, level=6, predictor_bits=0, entropy_bits=0, icc=None):
+    """dt_hip_webp_data_t for an Ansel WebP export.  src/imageio/format/webp.c was not at hand: its dialog is RECALLED,
+    not read -- `comp_type` 0 lossy, 1 lossless; `quality` 0..100 and `hint` (default, picture,
+    photo, graphic) steer libwebp's lossy encoder and its lossless effort and have no counterpart in the device's
+    encoder: they are accepted and ignored.  The device writes lossless only: comp_type 0 raises.  `level` 0..9 is the
+    device encoder's own effort (0 literals only, 1-3 greedy matching, 4-9 lazy); predictor_bits / entropy_bits 0
+    take the defaults.  icc: the output profile's bytes (an ICCP chunk), kept alive by the returned struct.  `capacity`
+    is left 0: set it to the output buffer's size (dt_hip_webp_bound())."""
+    if int(comp_type) != 1:
+        raise ValueError("WebP comp_type %r: the device writes lossless WebP only (comp_type 1); lossy VP8 is not built" % (comp_type,))
+    if not 0 <= int(quality) <= 100:
+        raise ValueError("WebP quality %r is outside 0..100" % (quality,))
+    if int(hint) not in (0, 1, 2, 3):
+        raise ValueError("WebP hint %r is not 0 (default), 1 (picture), 2 (photo) or 3 (graphic)" % (hint,))
+    lv = int(level)
+    if not 0 <= lv <= 9:
+        raise ValueError("WebP level %r is outside 0..9" % (level,))
+    for name, v in (("predictor_bits", predictor_bits), ("entropy_bits", entropy_bits)):
+        if int(v) != 0 and not 2 <= int(v) <= 9:
+            raise ValueError("WebP %s %r is neither 0 nor in 2..9" % (name, v))
+    d = abi.WebpData(lossless=1, level=lv, predictor_bits=int(predictor_bits), entropy_bits=int(entropy_bits))
+    if icc:
+        icc = bytes(icc)
+        d._icc = C.create_string_buffer(icc, len(icc))
+        d.icc = C.cast(d._icc, C.c_void_p)
+        d.icc_bytes = len(icc)
+    return d

@@ -22,6 +22,7 @@ MODULE_BPP = {
     "export_u8": (16, 4), "export_jpeg": (4, 0),
     "export_png": (4, 0),  # 8 bits: node_bytes_per_px() reads 8 B/px at 16 bits
     "export_tiff": (4, 0),  # 8 bits: node_bytes_per_px() reads 8 / 16 B/px at 16 / 32 bits
+    "export_webp": (4, 0),
 }
 
 
@@ -103,6 +104,23 @@ def with_tiff(nodes, tiff_data):
 def tiff_bound(width, height, tiff_data):
     """dt_hip_tiff_bound(): a capacity the encoder's output always fits"""
     return int(lib.load().dt_hip_tiff_bound(width, height, C.byref(tiff_data)))
+
+
+def with_webp(nodes, webp_data):
+    """the node list with its trailing export_u16 swapped for export_u8 + export_webp (webp_data: params.webp() or an
+    abi.WebpData, its capacity set -- webp_bound()).  The node's output is the little-endian uint64 file length, then the
+    file.  The other nodes are shared with `nodes`."""
+    if not nodes or nodes[-1].op != "export_u16":
+        raise ValueError("with_webp: the node list does not end in export_u16")
+    last = nodes[-1]
+    w, h = last.piece.roi_out.width, last.piece.roi_out.height
+    return list(nodes[:-1]) + [Node("export_u8", None, last.piece),
+                               Node("export_webp", webp_data, abi.Piece.make(w, h, channels=4))]
+
+
+def webp_bound(width, height, webp_data):
+    """dt_hip_webp_bound(): a capacity the encoder's output always fits"""
+    return int(lib.load().dt_hip_webp_bound(width, height, C.byref(webp_data)))
 
 
 def light_pipe_nodes(width, height, lut_target_ptr, lut_first, lut_coeffs, with_filmic=True, filmic=None,

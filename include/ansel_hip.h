@@ -525,6 +525,33 @@ size_t dt_hip_tiff_bound(int width, int height, const dt_hip_tiff_data_t *d); /*
 int dt_hip_export_tiff(int devid, int width, int height, const dt_hip_tiff_data_t *d, dt_hip_mem_t dev_in,
                        dt_hip_mem_t dev_out);
 
+/* WebP export on the device (ansel_amd/csrc/webp.hip): a lossless WebP (VP8L) file, the fourth format of the export
+ * dialog (src/imageio/format/webp.c).  A valid stream of our own, not libwebp's bytes: libwebp's decoder returns the
+ * input's RGB, every pixel.  dev_in_rgba8: width x height RGBA u8 (export_u8); alpha is ignored and coded as 255.  The
+ * file: RIFF / WEBP, with a profile a VP8X and an ICCP chunk, then one VP8L chunk -- SUBTRACT_GREEN, PREDICTOR (a mode
+ * per block of 2^predictor_bits squared pixels), backward references over the residual pixels, and five prefix codes
+ * per tile of 2^entropy_bits squared pixels.  No colour cache, cross-colour transform, palette,
+ * near-lossless, alpha, animation; EXIF / XMP chunks stay on the host; lossy VP8 is refused.  dev_out receives a
+ * little-endian uint64 file length L, then the L bytes of the file.  If 8 + L exceeds `capacity` the length word is
+ * UINT64_MAX and nothing is written past `capacity`; the call does not wait for the device, so the caller reads the
+ * word.  dt_hip_webp_bound(): a capacity that always suffices (0 for refused settings).  Refused with
+ * DT_HIP_INVALID_ARG: lossless != 1, a field outside its range, width or height outside 1..16383, entropy_bits that
+ * give more than 65536 tiles, an ICC profile above 16 MiB, a capacity below 8.  In a pipe: node "export_webp" (data
+ * dt_hip_webp_data_t), the last node, directly behind "export_u8"; its output is `capacity` bytes. */
+typedef struct dt_hip_webp_data_t
+{
+  int32_t lossless;       /* must be 1 */
+  int32_t level;          /* 0 literals only; 1-3 greedy, 4-9 lazy (a longer match at the next position wins) */
+  int32_t predictor_bits; /* 0: default (5); else 2..9 */
+  int32_t entropy_bits;   /* 0: default rule (the smallest of 6..9 with at most 4096 tiles); else 2..9 */
+  uint64_t capacity;      /* bytes of dev_out, the 8-byte length word included */
+  const void *icc;        /* host memory, may be NULL; copied by the call and by dt_hip_pipe_add_node */
+  uint64_t icc_bytes;
+} dt_hip_webp_data_t;
+size_t dt_hip_webp_bound(int width, int height, const dt_hip_webp_data_t *d); /* pure, no device */
+int dt_hip_export_webp(int devid, int width, int height, const dt_hip_webp_data_t *d, dt_hip_mem_t dev_in_rgba8,
+                       dt_hip_mem_t dev_out);
+
 /* diffuse or sharpen: process(), src/iop/diffuse.c:1155-1258 -> wavelets_process() (:978-1106),
  * decompose_2D_Bspline() (src/pixel/bspline.h:351-377), heat_PDE_diffusion() (diffuse.c:760-968).
  * The struct is dt_iop_diffuse_params_t (diffuse.c:76-105; commit_params memcpy's it, :133-138)
