@@ -8,6 +8,8 @@ DT_HIP_SUCCESS = 0
 DT_HIP_DEFAULT_ERROR = -999
 DT_HIP_SYSMEM_ALLOCATION = -998
 DT_HIP_INVALID_ARG = -997
+DT_HIP_WRITER_FAILED = -996
+DT_HIP_FILE_TOO_LARGE = -995
 
 DT_HIP_TYPE_FLOAT = 1
 DT_HIP_TYPE_UINT16 = 2

@@ -213,6 +213,12 @@ int bilat_band_splat(int devid, const dt_hip_piece_t *piece, const dt_hip_bilat_
 int bilat_band_finish(int devid, const dt_hip_piece_t *piece, const dt_hip_bilat_data_t *d, dt_hip_mem_t grid,
                       dt_hip_mem_t in_rows, dt_hip_mem_t out_rows, int row0, int rows);
 
+// file_copy.hip: the trimmed download of an exported file.  file_host_view(): the device view of a pinned, 16-byte aligned host
+// buffer of host_bytes >= 8, or DT_HIP_INVALID_ARG with "<who>: the reason"; file_to_host_launch(): the copy on stream s
+// (dev_file: the length word and the file in a buffer of `capacity` bytes; file_copy_body.h says what the host finds)
+int file_host_view(const char *who, int devid, void *host, size_t host_bytes, void **view);
+int file_to_host_launch(hipStream_t s, const void *dev_file, size_t capacity, void *view, size_t host_bytes);
+
 // Grid for a grid-stride streaming kernel: enough workgroups to fill 256 CUs x 8 and no more
 // (cdna_hip_programming.md Guideline 11).
 static inline unsigned stream_grid(size_t work_items, unsigned block)

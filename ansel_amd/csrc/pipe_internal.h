@@ -157,6 +157,14 @@ struct dt_hip_pipe_t
     }
     return true;
   }
+  // the pipe's output is a file -- a little-endian uint64 length word and that many bytes in a buffer of the encoder's bound -- and
+  // not a frame: what a batch in file mode downloads (pipe_batch.cpp, dt_hip_batch_set_file_output())
+  bool output_is_a_file() const
+  {
+    if(nodes.empty()) return false;
+    const ansel::op_t op = nodes.back().op;
+    return op == ansel::OP_EXPORT_JPEG || op == ansel::OP_EXPORT_PNG || op == ansel::OP_EXPORT_TIFF || op == ansel::OP_EXPORT_WEBP;
+  }
   // the same for the pipe's output: the group that writes it leaves the fourth channel to whoever owns that buffer (the batch
   // owns its slots' and clears them once: pipe_batch.cpp)
   bool output_keeps_the_callers_alpha() const

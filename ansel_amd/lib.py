@@ -173,6 +173,9 @@ def load():
         "dt_hip_batch_wait": (i, [vp, i]),
         "dt_hip_batch_drain": (i, [vp]),
         "dt_hip_batch_set_writer": (i, [vp, vp, vp]),
+        "dt_hip_batch_set_file_output": (i, [vp, sz]),
+        "dt_hip_batch_file_bytes": (i, [vp, i, P(sz)]),
+        "dt_hip_read_file_to_host": (i, [i, vp, sz, vp, sz]),
         "dt_hip_plan_bands": (i, [i, i, i, i, P(abi.Band)]),
         "dt_hip_band_halo_rows": (i, [C.c_char_p, P(abi.Piece), vp, sz]),
         "dt_hip_pipe_band_begin": (i, [vp, P(abi.Band), vp, P(abi.BandState)]),

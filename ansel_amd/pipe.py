@@ -206,6 +206,7 @@ class DevicePipe:
 
     def __init__(self, devid, nodes, fusion=True):
         self.lib = lib.load()
+        self.devid = devid
         self.nodes = nodes  # keeps the ctypes structs alive
         self.handle = self.lib.dt_hip_pipe_new(devid)
         if not self.handle:
@@ -225,6 +226,37 @@ class DevicePipe:
 
     def process(self, dev_in, dev_out):
         lib.check(self.lib.dt_hip_pipe_process(self.handle, dev_in, dev_out), "dt_hip_pipe_process")
+
+    READ_FILE_STAGING = 64 << 20
+
+    def read_file(self, dev_out_ptr, capacity, staging_bytes=None):
+        """the file a pipe that ends in export_jpeg / _png / _tiff / _webp left in dev_out_ptr (`capacity` bytes: the length
+        word, then the file) -> bytes.  dt_hip_read_file_to_host() moves the file and not the capacity, through a pinned
+        staging buffer of min(capacity, 64 MiB) (staging_bytes: another size); a longer file is read once more into a buffer
+        of the 8 + L the first call reported."""
+        devid = self.devid
+        nbytes = max(8, min(int(capacity), int(staging_bytes or self.READ_FILE_STAGING)))
+        for attempt in (0, 1):
+            # (a multiple of 16 so that nothing else shares the last 16-byte word; host_bytes itself stays within the capacity)
+            host = self.lib.dt_hip_alloc_host_pinned((nbytes + 15) & ~15)
+            if not host:
+                raise lib.AnselHipError("read_file: no pinned staging buffer of %d bytes" % nbytes)
+            try:
+                lib.check(self.lib.dt_hip_read_file_to_host(devid, dev_out_ptr, capacity, host, nbytes), "dt_hip_read_file_to_host")
+                if self.lib.dt_hip_finish(devid) != 1:
+                    raise lib.AnselHipError("read_file: dt_hip_finish failed: %s" % self.lib.dt_hip_last_error().decode())
+                n = C.c_uint64.from_address(host).value
+                if n == 2 ** 64 - 1:
+                    raise lib.AnselHipError("read_file: no file in the buffer (length word UINT64_MAX: the encoder refused the "
+                                            "frame, or its file does not fit the %d bytes of capacity)" % capacity)
+                if 8 + n <= nbytes:
+                    return C.string_at(host + 8, n)
+            finally:
+                self.lib.dt_hip_free_host_pinned(host)
+            if attempt:
+                break
+            nbytes = 8 + n
+        raise lib.AnselHipError("read_file: the file of %d bytes did not fit a staging buffer of %d" % (n, nbytes))
 
     def close(self):
         if self.handle:

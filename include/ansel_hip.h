@@ -37,6 +37,7 @@ extern "C" {
 #define DT_HIP_SYSMEM_ALLOCATION (-998)
 #define DT_HIP_INVALID_ARG (-997)
 #define DT_HIP_WRITER_FAILED (-996) /* a batch's writer callback returned non-zero (dt_hip_batch_set_writer) */
+#define DT_HIP_FILE_TOO_LARGE (-995) /* a batch in file mode: the frame's file did not fit host_bytes (dt_hip_batch_set_file_output) */
 #define DT_HIP_MAX_ERRORS 5 /* src/common/opencl.h:50 */
 
 /* opaque device allocation, stands for cl_mem */
@@ -225,6 +226,17 @@ int dt_hip_copy_device_to_host(int devid, void *host, dt_hip_mem_t device, int w
 int dt_hip_read_buffer_from_device(int devid, void *host, dt_hip_mem_t device, size_t offset, size_t size, int blocking);
 int dt_hip_write_buffer_to_device(int devid, const void *host, dt_hip_mem_t device, size_t offset, size_t size, int blocking);
 int dt_hip_enqueue_copy_buffer_to_buffer(int devid, dt_hip_mem_t src, dt_hip_mem_t dst, size_t srcoffset, size_t dstoffset, size_t size);
+/* The download of an exported file.  The file encoders (dt_hip_export_jpeg / _png / _tiff / _webp) leave a little-endian
+ * uint64 length word L and L file bytes in a device buffer of `capacity` bytes (their dt_hip_*_bound()); this moves
+ * 8 + L bytes and not the capacity.  L exists on the device alone when the copy is enqueued, so the copy is a kernel on the
+ * device's stream that stores through the device view of `host`: pinned (dt_hip_is_pinned_memory) over all of its
+ * host_bytes, 16-byte aligned as dev_file, capacity and host_bytes >= 8 -- anything else is DT_HIP_INVALID_ARG with a
+ * reason, and nothing is enqueued.  Returns without waiting; after dt_hip_finish() the host holds
+ *   the word L and the L file bytes, or
+ *   the word UINT64_MAX and nothing else: the device's word was UINT64_MAX (the encoder refused) or 8 + L > capacity, or
+ *   the true L and nothing else: the file fits the device buffer but 8 + L > host_bytes (call again with that much).
+ * The bytes behind what was written keep what they held. */
+int dt_hip_read_file_to_host(int devid, dt_hip_mem_t dev_file, size_t capacity, void *host, size_t host_bytes);
 /* copy a w x h window of `bpp`-byte pixels between two linear images (used by tiling and
  * by the row-band halo exchange) */
 int dt_hip_enqueue_copy_region(int devid, dt_hip_mem_t src, int src_width, int src_x, int src_y,
@@ -904,6 +916,18 @@ int dt_hip_batch_drain(dt_hip_batch_t *batch);
  * between frames: the call drains the batch first. */
 typedef int (*dt_hip_batch_writer_t)(void *user, long seq, void *host_out, size_t bytes);
 int dt_hip_batch_set_writer(dt_hip_batch_t *batch, dt_hip_batch_writer_t writer, void *user);
+/* File output: for a pipe whose last node is export_jpeg / _png / _tiff / _webp the download moves the frame's file --
+ * its length word L and L bytes -- and not out_bytes (dt_hip_read_file_to_host() on the download stream).  Every host_out
+ * then holds host_bytes (8 <= host_bytes <= out_bytes; 0 switches the mode off), pinned and 16-byte aligned -- submit
+ * refuses any other with DT_HIP_INVALID_ARG before it enqueues anything.  The writer is called with bytes = 8 + L.  A
+ * frame whose file does not fit host_bytes (or whose encoder refused: the word UINT64_MAX) is not given to the writer: its
+ * host_out holds the word alone and its dt_hip_batch_wait() returns DT_HIP_FILE_TOO_LARGE, as does a drain and the submit
+ * that needs the slot; the frames behind it are still written.  Between frames only: the call drains the batch first.
+ * Any other pipe, host_bytes < 8 and host_bytes > out_bytes are DT_HIP_INVALID_ARG with a reason.
+ * dt_hip_batch_file_bytes(): 8 + L of the last frame waited for in `slot` (its true L also when the file was too large;
+ * 8 when the encoder refused); DT_HIP_INVALID_ARG with file output off and for a slot that never held a frame. */
+int dt_hip_batch_set_file_output(dt_hip_batch_t *batch, size_t host_bytes);
+int dt_hip_batch_file_bytes(dt_hip_batch_t *batch, int slot, size_t *bytes);
 
 /* ---- 3b. one frame over several devices: row bands ---------------------------------------- */
 /* Replaces default_process_tiling_cl() / _default_process_tiling_cl_ptp() (src/develop/tiling.c:842,
